@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — frames/sec of the per-frame CRT effect chain on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4}] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4}] [--batch B] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path (k_phosphor -> k_warp per frame, enqueued back to back by
 crtfx_process_batch) over one batch of B synthetic frames already resident in HBM.  The default
@@ -10,6 +10,12 @@ configuration the metric is quoted on.  N > 1: one process per GPU (torch.distri
 frame batches are sharded with no data-path collective for persistence 0 (weak scaling: every
 rank processes its own B frames per step); --config 4 adds the one-frame persistence carry over
 RCCL.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times K steps and prints the line.  --full adds what the headline does
+not need: per-kernel HIP-event times and the `roofline` object (with the device-copy and Infinity-Cache
+ceilings it measures), per-rank GPU clock / power samples, two further timed regions (`repeat_values`)
+and the CPU baseline.  --dump-outputs DIR writes a fixed, seeded sample of the last timed step's output
+frames (rank 0's) as float32 .npy files: the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -301,6 +307,24 @@ class stdout_to_stderr:
         return False
 
 
+DUMP_SAMPLES = 1 << 22      # 16 MB of float32 values + 32 MB of float64 indices: inside the 64 MB an output dump may take
+
+
+def dump_outputs(out, path, seed=0):
+    """--dump-outputs: a fixed, seeded sample of `out` (the frames one step returned, uint8 or float16 (B, H, W, 3) on the device)
+    as float32 in path/frames_sample.npy, the flat indices it was taken at in path/frames_sample_index.npy (float64: exact below
+    2^53).  The whole output when it has no more than DUMP_SAMPLES values."""
+    n = out.numel()
+    if n <= DUMP_SAMPLES:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(seed).integers(0, n, DUMP_SAMPLES, dtype=np.int64))
+    vals = out.reshape(-1)[torch.from_numpy(idx).to(out.device)].float().cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "frames_sample.npy"), vals)
+    np.save(os.path.join(path, "frames_sample_index.npy"), idx.astype(np.float64))
+
+
 def cpu_model():
     try:
         for line in open("/proc/cpuinfo"):
@@ -318,9 +342,15 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", type=int, default=3, choices=[0, 2, 3, 4, 5], help="BASELINE.json configs[N-1]; 0 = the reference CLI's default flags at 1080p")
     ap.add_argument("--batch", type=int, default=0, help="frames per step per GPU (default: 1920 at 4K, 8192 at 1080p, 384 at 8K — sized so that the default 20 steps run >= 3 s)")
-    ap.add_argument("--cpu-frames", type=int, default=-1, help="frames in the CPU baseline sample (0 = skip)")
-    ap.add_argument("--no-profile", action="store_true", help="do not record per-kernel HIP events in the timed region")
-    ap.add_argument("--repeats", type=int, default=2, help="further timed regions of K steps after the reported one (spread only; 0 = none)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel HIP events + the roofline object, per-rank GPU telemetry, "
+                         "the repeat regions and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of the last timed step's output frames (rank 0) to DIR/*.npy as float32")
+    ap.add_argument("--cpu-frames", type=int, default=-1, help="--full: frames in the CPU baseline sample (0 = skip)")
+    ap.add_argument("--no-profile", action="store_true", help="--full: do not record per-kernel HIP events in the timed region")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="further timed regions of K steps after the reported one (spread only; default 2 with --full, else 0)")
     ap.add_argument("--tables-outside", action="store_true", help="build the per-frame host tables before the timed region (A/B of the host share)")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port when bench.py launches the ranks itself")
     ap.add_argument("--force-dist", action="store_true",
@@ -433,9 +463,10 @@ def main():
     # step s = round s of the frame-sharded render: rank r owns global frames [(s*world + r)*B, ... + B).
     # The per-frame host tables of a step (scanline row gains via np.sin, flicker factors, the ctypes frame records and
     # their upload) are built INSIDE the timed region, as a render has to; the GPU works on step s meanwhile.
-    n_regions = 1 + max(0, a.repeats)
+    n_regions = 1 + max(0, a.repeats if a.repeats is not None else (2 if a.full else 0))
     total_steps = a.warmup + a.steps * n_regions
     host_s = [0.0]
+    last_out = [None]                          # the frames the last finished step returned (--dump-outputs)
 
     def build_tables(s_):
         t = time.perf_counter()
@@ -446,10 +477,14 @@ def main():
         for s_ in range(total_steps):
             build_tables(s_)
 
+    def keep_last(done):
+        if done:
+            last_out[0] = done[-1][1]
+
     def one_step(s_):
         if not a.tables_outside:
             build_tables(s_)
-        render.submit_round(frames, s_)        # overlapped schedule when asked for (results one call late), else run_round
+        keep_last(render.submit_round(frames, s_))      # overlapped schedule when asked for (results one call late), else run_round
 
     def sync():
         torch.cuda.synchronize(device)
@@ -459,34 +494,35 @@ def main():
 
     for s in range(a.warmup):
         one_step(s)
-    render.flush()
+    keep_last(render.flush())
     sync()
+    prof = a.full and not a.no_profile
     # k_warp's yardstick, measured on this box between the warm-up and the timed region (rank 0; a child process, ~1 s)
     mall_now = None
-    if rank == 0 and rs.warp_strength != 0.0 and not a.no_profile:
+    if rank == 0 and rs.warp_strength != 0.0 and prof:
         mall_now = mall_ceiling(pipe.plan().get("group_max", 1), h, w)
     if dist is not None:
         dist.barrier()
-    prof = not a.no_profile
     region_dt = []
     kt = {}
     own_dt = None
-    telem = GpuTelemetry(device)
+    telem = GpuTelemetry(device) if a.full else None
     telem_first = None
     for reg in range(n_regions):
         first = a.warmup + reg * a.steps
         host_s[0] = 0.0
         if reg == 0:
             pipe.profile(8 if prof else 0)      # HIP events on the launches of every 8th frame of the reported region
-            telem.start()
+            if telem is not None:
+                telem.start()
         t0 = time.perf_counter()
         for s in range(first, first + a.steps):
             one_step(s)
-        render.flush()
+        keep_last(render.flush())
         sync()
         dt_r = time.perf_counter() - t0
         if reg == 0:
-            telem_first = telem.stop()
+            telem_first = telem.stop() if telem is not None else None
             kt = pipe.profile_read() if prof else {}
             pipe.profile(False)
             host_first = host_s[0]
@@ -498,6 +534,8 @@ def main():
             dt_r = float(t.item())
         region_dt.append(dt_r)
     dt = region_dt[0]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(last_out[0], a.dump_outputs)
 
     # what every rank saw of the reported region — frames/s on its own clock, its GPU's shader clock and package power, its kernel
     # time per launch group and (sharded persistence) its own hop / fix-up split: a sub-7x result at 8 GPUs can then be attributed from
@@ -659,7 +697,7 @@ def main():
             }
             # figures NOT measured in this run (another box of the same chip model): context only, never part of `roofline`
             res["reference_figures"] = {"mall_ceiling_committed": mall_ceiling_committed(fpl, h) if rs.warp_strength != 0.0 else None}
-        if world == 1 and a.cpu_frames != 0 and a.config != 5:
+        if a.full and world == 1 and a.cpu_frames != 0 and a.config != 5:
             n_cpu = a.cpu_frames if a.cpu_frames > 0 else (8 if h >= 2160 else 32)   # ~10-12 s of CPU work (single thread + the 2-worker repeat)
             v, secs, v2 = cpu_baseline(rs, h, w, fps, n_cpu)
             res["cpu_baseline"] = {"value": round(v, 4), "unit": "frames/s", "cores": 1, "kind": "port",

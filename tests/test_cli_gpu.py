@@ -287,7 +287,7 @@ def test_bench_launches_its_own_ranks(config, batch):
     root = os.path.dirname(HERE)
     env = dict(os.environ, CRTFX_DIST_BACKEND="gloo")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--config", str(config),
-           "--batch", str(batch), "--cpu-frames", "0", "--repeats", "0"]
+           "--batch", str(batch), "--full", "--cpu-frames", "0", "--repeats", "0"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -333,6 +333,58 @@ def test_bench_preflight_fails_fast_with_a_reason(case):
     assert r.returncode != 0 and took < 60, (r.returncode, took, r.stderr[-1500:])
     assert "bench.py preflight failed" in r.stderr and want in r.stderr, r.stderr[-1500:]
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]          # no result line
+
+
+def _bench_line(args, timeout=600):
+    import json
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py")] + args, capture_output=True, text=True, timeout=timeout)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+@pytest.mark.parametrize("config,batch", [(2, 4), (4, 26)])
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(pc, tmp_path, config, batch):
+    """`bench.py --gpus 1 --steps K --warmup W` times K steps and prints the headline fields only (no per-kernel events, roofline, GPU
+    telemetry, repeat regions or CPU baseline: those are --full's).  --dump-outputs DIR holds a seeded sample of the frames the last timed
+    step returned: the frames the in-order render of the same seeded inputs gives for that step (config 4: the persistence state carried
+    through every earlier step)."""
+    import bench
+    from pythoncrt_amd.pipeline import FramePipeline, baseline_config
+    steps, warmup = 2, 1
+    res = _bench_line(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--config", str(config), "--batch", str(batch),
+                       "--dump-outputs", str(tmp_path)])
+    assert res["steps"] == steps and res["warmup"] == warmup and res["unit"] == "frames/s" and res["higher_is_better"] is True
+    assert res["value"] > 0 and abs(res["ms_per_step"] * steps - res["timed_region_s"] * 1e3) <= 0.06      # both rounded to 1e-4
+    assert "roofline" not in res and "cpu_baseline" not in res and res["repeat_values"] == []
+    assert res["dist"]["per_rank"][0]["gpu"] is None and res["dist"]["per_rank"][0]["chain_ms_per_frame"] is None
+    vals = np.load(tmp_path / "frames_sample.npy")
+    idx = np.load(tmp_path / "frames_sample_index.npy")
+    assert vals.dtype == np.float32 and idx.dtype == np.float64 and vals.shape == idx.shape and vals.size > 0
+    assert sum(f.stat().st_size for f in tmp_path.iterdir()) <= 64 << 20
+    rs, h, w = baseline_config(config)
+    dev = torch.device("cuda", 0)
+    frames = bench.synth_frames(batch, h, w, dev, seed=1234)
+    pipe = FramePipeline(dev, h, w, rs, fps=30.0, noise_seed=1234)
+    state = None
+    for s in range(warmup + steps):
+        out, state = pipe.run(frames, first_index=s * batch, state=state)
+    exp = out.reshape(-1)[torch.from_numpy(idx.astype(np.int64)).to(dev)].float().cpu().numpy()
+    assert np.array_equal(vals, exp)
+
+
+def test_bench_full_adds_the_secondary_measurements(pc):
+    """--full: per-kernel HIP-event times and the roofline object, per-rank GPU telemetry, the repeat regions and the CPU baseline."""
+    res = _bench_line(["--gpus", "1", "--steps", "2", "--warmup", "1", "--config", "2", "--batch", "8", "--full", "--cpu-frames", "1"])
+    assert res["steps"] == 2 and len(res["repeat_values"]) == 2
+    r = res["roofline"]
+    assert r["kernels"] and r["achieved"] > 0 and r["copy_ceiling"] > 0 and r["plan"]
+    assert res["cpu_baseline"]["value"] > 0
+    pr = res["dist"]["per_rank"][0]
+    assert pr["chain_ms_per_frame"] > 0 and set(pr["gpu"]) >= {"samples", "sclk_mhz_mean", "power_w_mean"}
 
 
 @pytest.mark.parametrize("case", ["defaults", "gaussian_warp_text", "no_persistence_resized"])

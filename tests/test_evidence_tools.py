@@ -62,10 +62,10 @@ def test_source_hash_covers_every_kernel_source():
     assert len(h) == 16 and int(h, 16) >= 0
 
 
-def test_bench_ceiling_and_telemetry_degrade_gracefully():
-    """bench.py's round-4 additions on a box without a GPU: the committed Infinity-Cache-resident ceiling of another box is a reference figure
-    (4K groups, 1080p groups; nothing for other sizes), the one in `roofline` is measured in the run or absent, and the per-rank GPU telemetry turns into nulls with a note instead of raising
-    when rocm_smi / the device is unavailable."""
+def test_bench_ceiling_and_telemetry_degrade_gracefully(monkeypatch, tmp_path):
+    """bench.py's round-4 additions: the committed Infinity-Cache-resident ceiling of another box is a reference figure (4K groups, 1080p
+    groups; nothing for other sizes), the one in `roofline` is measured in the run or absent (no program, or no GPU), and the per-rank GPU
+    telemetry turns into nulls with a note instead of raising when rocm_smi / the device is unavailable."""
     import sys
     sys.path.insert(0, ROOT)
     import bench
@@ -79,8 +79,14 @@ def test_bench_ceiling_and_telemetry_degrade_gracefully():
     rows = bench._mall_rows("2 frame(s) (199 MB float32 just written) x3          36.5 us    6814 GB/s (source + uint8 out)\n"
                             "2 frame(s) (199 MB float32 just written) tap4        40.8 us    6095 GB/s (source + uint8 out)\n", 2)
     assert rows["x3"] == {"us_per_group": 36.5, "gbs": 6814.0} and rows["tap4"]["us_per_group"] == 40.8
-    assert bench.mall_ceiling(2.0, 2160, 3840) is None
     import torch
+    m = bench.mall_ceiling(2.0, 2160, 3840)
+    if torch.cuda.is_available() and os.access(bench.MALL_COPY_EXE, os.X_OK):       # the suite run on the GPU box, after build()
+        assert m and m["frames"] == 2 and m["gbs"] > 0 and m["us_per_group"] > 0 and "run on this box" in m["source"]
+    else:
+        assert m is None
+    monkeypatch.setattr(bench, "MALL_COPY_EXE", str(tmp_path / "no_mall_copy"))        # the program not built: no figure, on any box
+    assert bench.mall_ceiling(2.0, 2160, 3840) is None
     t = bench.GpuTelemetry(torch.device("cpu"))
     t.start()
     out = t.stop()
@@ -107,7 +113,7 @@ def test_committed_bench_lines_of_the_newest_round_carry_their_counters():
     PMC passes of those sources had been summarised: `roofline.traffic` is a number, its provenance names the build's hash (not `stale`), the
     bound is counter-derived and the plan is recorded.  Round 4 committed four lines that said `stale: true` / `bound: "hbm"`: the staleness
     guard had worked, nobody had re-taken the lines.  (A change to any hashed source — pythoncrt_amd/csrc/*, include/crtfx.h — means: run
-    tools/collect_profiles.sh + summarise_profiles.py per config, then `bench.py --config N` again, and commit the five lines.)"""
+    tools/collect_profiles.sh + summarise_profiles.py per config, then `bench.py --config N --full` again, and commit the five lines.)"""
     import glob
     import json
     import re
@@ -274,6 +280,30 @@ def test_bench_keeps_stdout_to_one_json_line_around_the_rccl_banner():
     import bench
     a = bench.parse_args(["--gpus", "1", "--force-dist", "--config", "4"])
     assert a.force_dist and a.gpus == 1 and a.config == 4
+
+
+def test_bench_plain_defaults_and_output_dump(tmp_path):
+    """A plain bench.py run carries no --full work and no repeat region unless asked; bench.dump_outputs writes the same seeded float32
+    sample of a step's frames every time (indices beside it), inside 64 MB, and the whole output when it is small."""
+    import numpy as np
+    import torch
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert not a.full and a.repeats is None and a.dump_outputs is None and a.steps == 5 and a.warmup == 2
+    a = bench.parse_args(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full and a.dump_outputs == str(tmp_path)
+    out = torch.randint(0, 256, (3, 720, 1280, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(5))
+    got = []
+    for d in ("a", "b"):
+        bench.dump_outputs(out, str(tmp_path / d))
+        got.append((np.load(tmp_path / d / "frames_sample.npy"), np.load(tmp_path / d / "frames_sample_index.npy")))
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= 64 << 20
+    (v, i), (v2, i2) = got
+    assert v.dtype == np.float32 and i.dtype == np.float64 and np.array_equal(v, v2) and np.array_equal(i, i2)
+    assert v.size > bench.DUMP_SAMPLES // 2 and np.array_equal(v, out.reshape(-1).numpy()[i.astype(np.int64)].astype(np.float32))
+    small = out[:1, :8].contiguous().half()
+    bench.dump_outputs(small, str(tmp_path / "c"))
+    assert np.array_equal(np.load(tmp_path / "c" / "frames_sample.npy"), small.reshape(-1).float().numpy())
 
 
 def _synthetic_line(n, value, clk=2250.0, pw=1320.0, own=None, chain=0.0194, sched=None, workload="BASELINE configs[3]: 1920x1080 chain, persistence 0.5, u8 in/out"):

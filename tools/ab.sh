@@ -6,7 +6,7 @@
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$PWD}; OUT=$R/gpurun_out; TAG=$1; FL=$2; shift; shift; mkdir -p $OUT
 [ $# -eq 0 ] && set -- ""
-B="--steps 6 --warmup 2 --cpu-frames 0 --repeats 1 $FL"
+B="--full --steps 6 --warmup 2 --cpu-frames 0 --repeats 1 $FL"
 line() { python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d.get('roofline',{}); k=r.get('kernels',{})

@@ -5,7 +5,7 @@ set -o pipefail
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out; TAG=${1:-r06}
 F=$OUT/${TAG}_ab_fused.txt
 : > $F
-one() { python3 $R/bench.py --config 0 --cpu-frames 0 --repeats 1 "$@" 2>/dev/null | python3 -c "
+one() { python3 $R/bench.py --config 0 --full --cpu-frames 0 --repeats 1 "$@" 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 r = d['roofline']

@@ -5,7 +5,7 @@ for v in "$@"; do
   lib=""; [ "$v" != base ] && lib="$R/build/ab/lib_$v.so"
   for cfg in 2 5 4; do
     b=256; [ $cfg = 5 ] && b=16
-    CRTFX_LIB=$lib timeout -k 10 150 python bench.py --config $cfg --steps 8 --warmup 2 --repeats 0 --cpu-frames 0 --batch $b > $OUT/abrr_${v}_c$cfg.json 2>/dev/null
+    CRTFX_LIB=$lib timeout -k 10 150 python bench.py --config $cfg --full --steps 8 --warmup 2 --repeats 0 --cpu-frames 0 --batch $b > $OUT/abrr_${v}_c$cfg.json 2>/dev/null
   done
 done
 python - <<PY

@@ -2,7 +2,7 @@
 # Run on the GPU box (gpurun): collects the rocprofv3 evidence bench.py's roofline object refers to.
 # Usage: bash tools/collect_profiles.sh <tag> [bench flags, e.g. --config 2]    -> gpurun_out/<tag>_*   (then tools/summarise_profiles.py <tag> [configN] here)
 # After a source change the bench line taken HERE still carries the previous build's traffic.json (nulled as stale): once
-# summarise_profiles.py has written the new one, take `python bench.py > gpurun_out/<tag>_bench.json` again and copy it to profiles/.
+# summarise_profiles.py has written the new one, take the `bench.py --full` line of this script again and copy it to profiles/.
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$PWD}
 TAG=${1:-r02_z}
@@ -17,8 +17,8 @@ cd /tmp && export TMPDIR=/tmp
 PMC_BATCH=${PMC_BATCH:-256}
 echo $PMC_BATCH > $OUT/${TAG}_pmc_batch.txt
 PB="--steps 2 --warmup 1 --batch $PMC_BATCH --repeats 0 --cpu-frames 0 --no-profile"
-timeout -k 10 300 python3 $R/bench.py $X > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_trace -- python3 $R/bench.py $X --steps 10 --repeats 0 --cpu-frames 0 > $OUT/${TAG}_trace.log 2>&1
+timeout -k 10 300 python3 $R/bench.py $X --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_trace -- python3 $R/bench.py $X --full --steps 10 --repeats 0 --cpu-frames 0 > $OUT/${TAG}_trace.log 2>&1
 rm -f $OUT/${TAG}_trace/*/*kernel_trace.csv      # the per-dispatch trace (tens of MB) is not needed: the stats CSV is what gets committed
 timeout -k 10 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/${TAG}_fetch -- python3 $R/bench.py $X $PB > $OUT/${TAG}_fetch.log 2>&1
 timeout -k 10 200 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/${TAG}_write -- python3 $R/bench.py $X $PB > $OUT/${TAG}_write.log 2>&1

@@ -13,7 +13,7 @@ for c in 3 0 2 4 5; do
   t=$TAG; [ $c != 3 ] && t=${TAG}_c$c
   bash tools/collect_profiles.sh $t --config $c > $OUT/${t}_collect.log 2>&1
   python3 tools/summarise_profiles.py $t config$c > $OUT/${t}_summarise.log 2>&1
-  timeout -k 10 300 python3 bench.py --config $c > $OUT/${t}_bench_final.json 2> $OUT/${t}_bench_final.err
+  timeout -k 10 300 python3 bench.py --config $c --full > $OUT/${t}_bench_final.json 2> $OUT/${t}_bench_final.err
   tail -1 $OUT/${t}_bench_final.json > $OUT/profiles_out/${t}_bench.json
   cp profiles/${t}_kernel_stats.csv profiles/${t}_pmc.json profiles/${t}_fetch_calibration.txt $OUT/profiles_out/ 2>/dev/null
   echo "config $c done: $(python3 -c "import json; d=json.load(open('$OUT/profiles_out/${t}_bench.json')); r=d['roofline']; print(d['value'], r['bound'], r['frac'], r['traffic_source'].get('source_hash'), {k: round(v['avg_launch_ms'] * 1e3, 1) for k, v in r['kernels'].items()})")"

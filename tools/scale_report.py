@@ -3,7 +3,7 @@
 the target — where the loss went.  The run sheet of DESIGN.md section 7 as a program: for whoever takes the 8-GPU measurement, once.
 
     python tools/scale_report.py line_n1.json line_n2.json ... [--target 7.0]
-    python bench.py --gpus 8 --config 4 | python tools/scale_report.py line_n1.json -        ('-' = a line on stdin)
+    python bench.py --gpus 8 --config 4 --full | python tools/scale_report.py line_n1.json -        ('-' = a line on stdin)
 
 Every file holds one bench.py JSON line (other lines are ignored), or a driver record with the line under "parsed".  No GPU, no torch.
 SURVEY 8e / north_star: ">= 7x frames/sec at 8 GPUs vs 1 GPU on the frame-sharded path" (crt_filter.py ref:1015-1017, :1081-1105 is the
