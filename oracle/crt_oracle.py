@@ -20,7 +20,9 @@ Parity status
   installable here; the reference ships no tests or golden vectors).  They restate OpenCV 4.x's
   published algorithms (see crt_oracle.c header) and are cross-checked against scipy/torch.
 * cv2.randn is not reproducible even in the reference (unseeded thread-local RNG), so the
-  oracle takes the N(0,1) plane as an argument (`noise_plane`).
+  oracle takes the N(0,1) plane as an argument (`noise_plane`).  The library's own generator is
+  restated in float64 by tests/grain_model.py, whose planes are fed here to check every kernel
+  build's in-kernel draw (tests/test_grain_gpu.py).
 
 dtype flow follows NumPy 2 promotion (numpy 2.2 is what runs here): python floats are weak, the
 f64 vignette mask (ref:267-275) and the np.float64 flicker factor (ref:632) promote the image to
