@@ -2,6 +2,7 @@
 parsing, on CPU.  A silent fallback here changes a committed number (round 3: function labels with a trailing comment were not
 recognised and every kernel was priced at the 2.9-cycle default)."""
 import os
+import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -235,6 +236,33 @@ def test_kernel_lds_query_arguments():
     assert lib.crtfx_kernel_lds_bytes(b"k_phosphor_ct", 16, 0) == -3 and lib.crtfx_kernel_lds_bytes(b"k_phosphor_ct", 0, 0) == -3
     assert lib.crtfx_kernel_lds_bytes(b"k_phosphor_ct", 9, 7) == -1 and lib.crtfx_kernel_lds_bytes(None, 9, 0) == -1
     assert lib.crtfx_kernel_lds_bytes(b"k_nothing", 9, 0) == -3 and lib.crtfx_kernel_lds_bytes(b"k_phosphor_cc", 20, 0) > 40960
+
+
+def phosphor_inventory(lib_path):
+    """(instances in the library that no row of tests/radius_builds.BUILDS covers, instances a row names that the library lacks)."""
+    import kernel_resources
+    from tests import radius_builds
+    have = {k for k in kernel_resources.resources(lib_path) if re.match(r"crtfx::k_phosphor(_[a-z]+)?<", k)}
+    want = radius_builds.covered_instances()
+    return sorted(have - want), sorted(want - have)
+
+
+def test_every_phosphor_build_has_a_gpu_sweep_row():
+    """Every crtfx::k_phosphor* instance compiled into libcrtfx.so (150 k_phosphor_rr, 30 k_phosphor_cc, 30 k_phosphor_ct and k_phosphor<-1>)
+    is a row of the table tests/test_radius_builds_gpu.py holds to the oracle, and every row names a build the library has: a radius or a
+    variant added to crtfx_rr.hip fails here, on the CPU, until the GPU sweep covers it."""
+    from pythoncrt_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build()
+    uncovered, missing = phosphor_inventory(_lib.LIB_PATH)
+    assert not uncovered, f"k_phosphor builds with no row in tests/radius_builds.BUILDS: {uncovered}"
+    assert not missing, f"rows of tests/radius_builds.BUILDS naming builds the library lacks: {missing}"
+
+
+def test_phosphor_sf_words_come_from_the_sources():
+    from tests import radius_builds
+    w = radius_builds.sf_words()
+    assert w["runtime"] == 0xFFFFFFFF and w["full+pixelate"] == w["full"] | (1 << 15) and w["full"] & (1 << 4) and not w["full"] & (1 << 14)
 
 
 def test_pmc_vmem_aggregator_refuses_a_missing_pass(tmp_path):
