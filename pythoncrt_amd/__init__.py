@@ -2,12 +2,14 @@
 
     from pythoncrt_amd import apply_crt_effect, apply_static_effects, make_triad_mask, make_vignette
     from pythoncrt_amd import process_frames      # the loop of process_video (ref:1037-1131) over the caller's frame iterator and writer
+    from pythoncrt_amd import IngestResize        # its first step (ref:1039-1041) on the device: Pillow's BILINEAR resize of uint8 frames
 
 See DESIGN.md (path, kernels, roofline) and INTEGRATION.md (how the reference binds to it).
 """
 from .effects import (DeviceState, TriadMask, VignetteMask, apply_crt_effect, apply_static_effects, make_triad_mask,
                       make_vignette)
+from .ingest import IngestResize
 from .render import iter_rgb24, process_frames
 
 __all__ = ["DeviceState", "TriadMask", "VignetteMask", "apply_crt_effect", "apply_static_effects", "make_triad_mask", "make_vignette",
-           "process_frames", "iter_rgb24"]
+           "process_frames", "iter_rgb24", "IngestResize"]

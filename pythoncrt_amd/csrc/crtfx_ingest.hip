@@ -1,0 +1,404 @@
+// crtfx_ingest.hip — the ingest stage of libcrtfx.so (include/crtfx_ingest.h): Pillow's 8-bit BILINEAR resize of uint8 RGB
+// frames on the device.  A translation unit of its own: it shares no kernel, table or handle with the effect chain.
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "crtfx_ingest.h"
+
+namespace crtfx_ingest_impl {
+
+constexpr int BLOCK = 256;
+constexpr int PREC = 22;                       // Pillow's PRECISION_BITS (32 - 8 - 2)
+constexpr unsigned HALF = 1u << (PREC - 1);
+constexpr int LDS_BUDGET = 40960;              // four blocks per CU (160 KB of LDS)
+constexpr size_t SCRATCH_BYTES = 64u << 20;    // general path: frames per group = what fits this much horizontal-pass scratch (at least one, at most 64)
+
+struct Axis { const int32_t* min; const int32_t* count; const int32_t* k; int ksize; };
+
+struct Args {
+    const uint8_t* src; size_t src_stride;
+    uint8_t* dst; size_t dst_stride;
+    int sh, sw, dh, dw;
+    Axis x, y;
+    int TH, TW;                // output rows / columns per tile
+    int P, HP;                 // LDS bytes per staged source row / per row of the horizontal result (multiples of 4)
+    int nr_max;                // source rows of the tallest tile
+    int sh_stage, sh_h, sh_v;  // log2 of the work items per row of the three phases (power-of-two rows: item -> (row, column) is a shift and a mask)
+};
+
+__device__ __forceinline__ unsigned clamp8(unsigned acc) { unsigned v = acc >> PREC; return v > 255u ? 255u : v; }
+
+// One block = TH output rows x TW output columns of one frame.
+//   phase 0  the tile's slice of the six tables -> LDS
+//   phase 1  the source rows / columns its taps reach -> LDS, as aligned dwords (a row keeps its global address modulo 4, so a
+//            dword in LDS is a dword in memory; only a dword that sticks out of the frame's own bytes is assembled from byte loads)
+//   phase 2  horizontal pass, one thread per (source row, output pixel): three 24-bit multiply-adds per tap, uint8 result -> LDS
+//   phase 3  vertical pass, one thread per ALIGNED dword of an output row (the bytes in front of the first and behind the last
+//            aligned dword of the tile's row segment are single-byte items): per tap two LDS dwords funnel-shifted to the row's phase
+__global__ __launch_bounds__(BLOCK) void k_ingest_fused(Args a) {
+    extern __shared__ __align__(16) unsigned char lds[];
+    const int tid = threadIdx.x;
+    const int ox0 = blockIdx.x * a.TW, oy0 = blockIdx.y * a.TH;
+    const int ow = min(a.TW, a.dw - ox0), oh = min(a.TH, a.dh - oy0);
+    const uint8_t* fsrc = a.src + (size_t)blockIdx.z * a.src_stride;
+    const uint8_t* fend = fsrc + (size_t)a.sh * a.sw * 3;
+    uint8_t* fdst = a.dst + (size_t)blockIdx.z * a.dst_stride;
+
+    int* s_xmin = reinterpret_cast<int*>(lds);
+    int* s_xcnt = s_xmin + a.TW;
+    int* s_kx = s_xcnt + a.TW;
+    int* s_ymin = s_kx + a.TW * a.x.ksize;
+    int* s_ycnt = s_ymin + a.TH;
+    int* s_ky = s_ycnt + a.TH;
+    unsigned* S = reinterpret_cast<unsigned*>(s_ky + a.TH * a.y.ksize);
+    unsigned* Hb = S + (size_t)a.nr_max * (a.P >> 2);
+
+    // min and min + count are non-decreasing (checked by crtfx_ingest_create): the tile's source window is first tap .. last tap
+    const int sx0 = a.x.min[ox0], sx1 = a.x.min[ox0 + ow - 1] + a.x.count[ox0 + ow - 1];
+    const int sy0 = a.y.min[oy0], sy1 = a.y.min[oy0 + oh - 1] + a.y.count[oy0 + oh - 1];
+    const int nr = sy1 - sy0, sb = (sx1 - sx0) * 3;
+
+    for (int i = tid; i < ow; i += BLOCK) { s_xmin[i] = a.x.min[ox0 + i] - sx0; s_xcnt[i] = a.x.count[ox0 + i]; }
+    for (int i = tid; i < ow * a.x.ksize; i += BLOCK) s_kx[i] = a.x.k[(size_t)ox0 * a.x.ksize + i];
+    for (int i = tid; i < oh; i += BLOCK) { s_ymin[i] = a.y.min[oy0 + i] - sy0; s_ycnt[i] = a.y.count[oy0 + i]; }
+    for (int i = tid; i < oh * a.y.ksize; i += BLOCK) s_ky[i] = a.y.k[(size_t)oy0 * a.y.ksize + i];
+
+    const size_t srow = (size_t)a.sw * 3;
+    for (int idx = tid; idx < (nr << a.sh_stage); idx += BLOCK) {
+        const int r = idx >> a.sh_stage, d = idx & ((1 << a.sh_stage) - 1);
+        const uint8_t* g = fsrc + (size_t)(sy0 + r) * srow + (size_t)sx0 * 3;
+        const unsigned lead = (unsigned)(reinterpret_cast<uintptr_t>(g) & 3u);
+        if (d < (int)((lead + sb + 3) >> 2)) {
+            const uint8_t* p = g - lead + 4 * d;
+            unsigned v;
+            if (p >= fsrc && p + 4 <= fend) {
+                v = *reinterpret_cast<const unsigned*>(p);
+            } else {
+                v = 0;
+                for (int e = 0; e < 4; ++e)
+                    if (p + e >= fsrc && p + e < fend) v |= (unsigned)p[e] << (8 * e);
+            }
+            S[r * (a.P >> 2) + d] = v;
+        }
+    }
+    __syncthreads();
+
+    const unsigned char* Sb = reinterpret_cast<const unsigned char*>(S);
+    unsigned char* Hbb = reinterpret_cast<unsigned char*>(Hb);
+    for (int idx = tid; idx < (nr << a.sh_h); idx += BLOCK) {
+        const int r = idx >> a.sh_h, p = idx & ((1 << a.sh_h) - 1);
+        if (p < ow) {
+            const unsigned lead = (unsigned)(reinterpret_cast<uintptr_t>(fsrc + (size_t)(sy0 + r) * srow + (size_t)sx0 * 3) & 3u);
+            const unsigned char* s = Sb + r * a.P + lead + s_xmin[p] * 3;
+            const int* k = s_kx + p * a.x.ksize;
+            const int cnt = s_xcnt[p];
+            unsigned a0 = HALF, a1 = HALF, a2 = HALF;
+            for (int t = 0; t < cnt; ++t) {
+                const unsigned kk = (unsigned)k[t];
+                a0 += __umul24(kk, s[3 * t]);
+                a1 += __umul24(kk, s[3 * t + 1]);
+                a2 += __umul24(kk, s[3 * t + 2]);
+            }
+            unsigned char* o = Hbb + r * a.HP + p * 3;
+            o[0] = (unsigned char)clamp8(a0); o[1] = (unsigned char)clamp8(a1); o[2] = (unsigned char)clamp8(a2);
+        }
+    }
+    __syncthreads();
+
+    const int nb = ow * 3;
+    const size_t drow = (size_t)a.dw * 3;
+    for (int idx = tid; idx < (oh << a.sh_v); idx += BLOCK) {
+        const int y = idx >> a.sh_v, i = idx & ((1 << a.sh_v) - 1);
+        uint8_t* g = fdst + (size_t)(oy0 + y) * drow + (size_t)ox0 * 3;
+        const int lead = min(nb, (int)((4u - (unsigned)(reinterpret_cast<uintptr_t>(g) & 3u)) & 3u));
+        const int nd = (nb - lead) >> 2;
+        const int* k = s_ky + y * a.y.ksize;
+        const int cnt = s_ycnt[y];
+        const int r0 = s_ymin[y];
+        if (i < nd) {
+            const int o = lead + 4 * i;                       // byte offset in the tile's row; o + 3 < nb
+            const unsigned* h = Hb + r0 * (a.HP >> 2) + (o >> 2);
+            const unsigned sh8 = (unsigned)(o & 3) * 8u;
+            unsigned a0 = HALF, a1 = HALF, a2 = HALF, a3 = HALF;
+            for (int t = 0; t < cnt; ++t) {
+                const unsigned kk = (unsigned)k[t];
+                unsigned v = h[0];
+                if (sh8) v = (v >> sh8) | (h[1] << (32u - sh8));   // h[1] lies inside the row's pitch (HP = round4(3 * TW) + 4)
+                a0 += __umul24(kk, v & 255u);
+                a1 += __umul24(kk, (v >> 8) & 255u);
+                a2 += __umul24(kk, (v >> 16) & 255u);
+                a3 += __umul24(kk, v >> 24);
+                h += a.HP >> 2;
+            }
+            *reinterpret_cast<unsigned*>(g + o) = clamp8(a0) | (clamp8(a1) << 8) | (clamp8(a2) << 16) | (clamp8(a3) << 24);
+        } else if (i < nd + (nb - 4 * nd)) {
+            const int e = i - nd;
+            const int o = e < lead ? e : 4 * nd + e;           // the head bytes, then the tail behind the last aligned dword
+            const unsigned char* h = Hbb + r0 * a.HP + o;
+            unsigned acc = HALF;
+            for (int t = 0; t < cnt; ++t) { acc += __umul24((unsigned)k[t], h[0]); h += a.HP; }
+            g[o] = (uint8_t)clamp8(acc);
+        }
+    }
+}
+
+// General path, any tap count.  Horizontal pass: one thread per output pixel of a source row, taps read from memory.
+__global__ __launch_bounds__(BLOCK) void k_ingest_h(const uint8_t* src, size_t src_stride, uint8_t* tmp, int sh, int sw, int dw, Axis x) {
+    const int px = blockIdx.x * BLOCK + threadIdx.x;
+    if (px >= dw) return;
+    const uint8_t* s = src + (size_t)blockIdx.z * src_stride + ((size_t)blockIdx.y * sw + x.min[px]) * 3;
+    const int32_t* k = x.k + (size_t)px * x.ksize;
+    const int cnt = x.count[px];
+    unsigned a0 = HALF, a1 = HALF, a2 = HALF;
+    for (int t = 0; t < cnt; ++t) {
+        const unsigned kk = (unsigned)k[t];
+        a0 += __umul24(kk, s[3 * t]);
+        a1 += __umul24(kk, s[3 * t + 1]);
+        a2 += __umul24(kk, s[3 * t + 2]);
+    }
+    uint8_t* o = tmp + (((size_t)blockIdx.z * sh + blockIdx.y) * dw + px) * 3;
+    o[0] = (uint8_t)clamp8(a0); o[1] = (uint8_t)clamp8(a1); o[2] = (uint8_t)clamp8(a2);
+}
+
+// Vertical pass: one thread per output byte of an output row (consecutive lanes, consecutive bytes).
+__global__ __launch_bounds__(BLOCK) void k_ingest_v(const uint8_t* tmp, uint8_t* dst, size_t dst_stride, int sh, int dw, Axis y) {
+    const int j = blockIdx.x * BLOCK + threadIdx.x;
+    const size_t row = (size_t)dw * 3;
+    if ((size_t)j >= row) return;
+    const int oy = blockIdx.y;
+    const uint8_t* s = tmp + ((size_t)blockIdx.z * sh + y.min[oy]) * row + j;
+    const int32_t* k = y.k + (size_t)oy * y.ksize;
+    const int cnt = y.count[oy];
+    unsigned acc = HALF;
+    for (int t = 0; t < cnt; ++t) { acc += __umul24((unsigned)k[t], s[0]); s += row; }
+    dst[(size_t)blockIdx.z * dst_stride + (size_t)oy * row + j] = (uint8_t)clamp8(acc);
+}
+
+}  // namespace crtfx_ingest_impl
+
+using namespace crtfx_ingest_impl;
+
+struct crtfx_ingest {
+    int device = 0;
+    int sh = 0, sw = 0, dh = 0, dw = 0;
+    int32_t* tables = nullptr;          // one device allocation: x min | x count | x k | y min | y count | y k
+    Axis x{}, y{};
+    bool fused_fits = false;            // some tile shape meets the LDS budget
+    Args fused{};                       // its launch constants (frame pointers filled per run)
+    int lds_bytes = 0;
+    uint8_t* scratch = nullptr;         // general path: scratch_frames x sh x dw x 3
+    int scratch_frames = 0;
+    bool force_general = false;
+    char plan[128] = "";
+    std::string err;
+};
+
+namespace {
+
+thread_local std::string g_create_err;
+
+int fail(crtfx_ingest* p, int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (p) p->err = buf; else g_create_err = buf;
+    return code;
+}
+
+struct DeviceGuard {
+    int prev = -1;
+    bool switched = false;
+    hipError_t err = hipSuccess;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) { err = hipSetDevice(dev); switched = err == hipSuccess; }
+    }
+    ~DeviceGuard() { if (switched && prev >= 0) (void)hipSetDevice(prev); }
+};
+
+int log2_ceil(int v) { int s = 0; while ((1 << s) < v) ++s; return s; }
+
+// the rules crtfx_ingest.h states for a table; the kernels' bounds rest on them
+const char* check_axis(const int32_t* mn, const int32_t* cnt, const int32_t* k, int ksize, int n_in, int n_out) {
+    for (int i = 0; i < n_out; ++i) {
+        if (mn[i] < 0 || cnt[i] < 1 || cnt[i] > ksize || mn[i] > n_in - cnt[i]) return "a tap window leaves the source (min >= 0, 1 <= count <= ksize, min + count <= n_in)";
+        if (i && (mn[i] < mn[i - 1] || mn[i] + cnt[i] < mn[i - 1] + cnt[i - 1])) return "min and min + count must be non-decreasing";
+        for (int t = 0; t < cnt[i]; ++t)
+            if (k[(size_t)i * ksize + t] < 0 || k[(size_t)i * ksize + t] >= (1 << 24)) return "a coefficient is outside [0, 2^24)";
+    }
+    return nullptr;
+}
+
+// largest source extent (taps of the first .. last output index) over the tiles of `tile` output indices
+int max_extent(const int32_t* mn, const int32_t* cnt, int n_out, int tile) {
+    int m = 0;
+    for (int o = 0; o < n_out; o += tile) {
+        const int last = (o + tile < n_out ? o + tile : n_out) - 1;
+        const int e = mn[last] + cnt[last] - mn[o];
+        if (e > m) m = e;
+    }
+    return m;
+}
+
+void plan_fused(crtfx_ingest* p, const int32_t* xmin, const int32_t* xcnt, const int32_t* ymin, const int32_t* ycnt) {
+    static const int shapes[][2] = {{32, 128}, {32, 64}, {16, 128}, {16, 64}, {8, 64}, {8, 32}, {4, 32}};
+    for (const auto& s : shapes) {
+        const int TH = s[0], TW = s[1];
+        const int rows = TH < p->dh ? TH : p->dh, cols = TW < p->dw ? TW : p->dw;
+        const long long nr = max_extent(ymin, ycnt, p->dh, TH), nc = max_extent(xmin, xcnt, p->dw, TW);
+        const long long P = (3 * nc + 3 + 3) & ~3LL, HP = ((3LL * cols + 3) & ~3LL) + 4;
+        const long long tab = 4LL * (2 * cols + (long long)cols * p->x.ksize + 2 * rows + (long long)rows * p->y.ksize);
+        const long long total = tab + nr * (P + HP);
+        if (total > LDS_BUDGET) continue;
+        Args& a = p->fused;
+        a = Args{};
+        a.sh = p->sh; a.sw = p->sw; a.dh = p->dh; a.dw = p->dw;
+        a.TH = rows; a.TW = cols; a.P = (int)P; a.HP = (int)HP; a.nr_max = (int)nr;
+        a.sh_stage = log2_ceil((int)(P >> 2));
+        a.sh_h = log2_ceil(cols);
+        a.sh_v = log2_ceil((3 * cols) / 4 + 6);
+        p->lds_bytes = (int)total;
+        p->fused_fits = true;
+        return;
+    }
+}
+
+void note_plan(crtfx_ingest* p, int frames) {
+    if (p->fused_fits && !p->force_general)
+        snprintf(p->plan, sizeof p->plan, "ingest=k_ingest_fused<rows=%d,cols=%d>;lds=%d;frames=%d", p->fused.TH, p->fused.TW, p->lds_bytes, frames);
+    else
+        snprintf(p->plan, sizeof p->plan, "ingest=k_ingest_h+k_ingest_v;frames=%d", frames);
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* crtfx_ingest_last_error(const crtfx_ingest* p) { return p ? p->err.c_str() : g_create_err.c_str(); }
+
+int crtfx_ingest_create(int device, int src_h, int src_w, int dst_h, int dst_w, int pix_fmt,
+                        const int32_t* x_min, const int32_t* x_count, const int32_t* x_k, int x_ksize,
+                        const int32_t* y_min, const int32_t* y_count, const int32_t* y_k, int y_ksize, crtfx_ingest** out_plan) {
+    g_create_err.clear();
+    if (!out_plan) return fail(nullptr, CRTFX_E_INVALID, "out_plan is null");
+    *out_plan = nullptr;
+    if (pix_fmt == CRTFX_PIX_F16) return fail(nullptr, CRTFX_E_UNSUPPORTED, "only uint8 RGB frames are resized (Pillow has no half image)");
+    if (pix_fmt != CRTFX_PIX_U8) return fail(nullptr, CRTFX_E_INVALID, "unknown pixel format %d", pix_fmt);
+    if (src_h < 1 || src_w < 1 || dst_h < 1 || dst_w < 1 || src_h > 32767 || src_w > 32767 || dst_h > 32767 || dst_w > 32767)
+        return fail(nullptr, CRTFX_E_INVALID, "sizes %dx%d -> %dx%d outside 1..32767", src_h, src_w, dst_h, dst_w);
+    if (!x_min || !x_count || !x_k || !y_min || !y_count || !y_k) return fail(nullptr, CRTFX_E_INVALID, "a table is null");
+    if (x_ksize < 1 || y_ksize < 1) return fail(nullptr, CRTFX_E_INVALID, "ksize %d / %d < 1", x_ksize, y_ksize);
+    if (const char* why = check_axis(x_min, x_count, x_k, x_ksize, src_w, dst_w)) return fail(nullptr, CRTFX_E_INVALID, "x tables: %s", why);
+    if (const char* why = check_axis(y_min, y_count, y_k, y_ksize, src_h, dst_h)) return fail(nullptr, CRTFX_E_INVALID, "y tables: %s", why);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(nullptr, CRTFX_E_HIP, "no HIP device %d", device);
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return fail(nullptr, CRTFX_E_HIP, "hipSetDevice(%d): %s", device, hipGetErrorString(guard.err));
+    crtfx_ingest* p = new (std::nothrow) crtfx_ingest();
+    if (!p) return fail(nullptr, CRTFX_E_NOMEM, "out of host memory");
+    p->device = device; p->sh = src_h; p->sw = src_w; p->dh = dst_h; p->dw = dst_w;
+    p->x.ksize = x_ksize; p->y.ksize = y_ksize;
+    plan_fused(p, x_min, x_count, y_min, y_count);
+
+    std::vector<int32_t> host;
+    host.reserve((size_t)dst_w * (2 + x_ksize) + (size_t)dst_h * (2 + y_ksize));
+    host.insert(host.end(), x_min, x_min + dst_w);
+    host.insert(host.end(), x_count, x_count + dst_w);
+    host.insert(host.end(), x_k, x_k + (size_t)dst_w * x_ksize);
+    host.insert(host.end(), y_min, y_min + dst_h);
+    host.insert(host.end(), y_count, y_count + dst_h);
+    host.insert(host.end(), y_k, y_k + (size_t)dst_h * y_ksize);
+    const size_t frame_tmp = (size_t)src_h * dst_w * 3;
+    p->scratch_frames = p->fused_fits ? 1 : (int)(SCRATCH_BYTES / frame_tmp);      // behind a fused plan the general path is an A/B switch only
+    if (p->scratch_frames < 1) p->scratch_frames = 1;
+    if (p->scratch_frames > 64) p->scratch_frames = 64;
+    hipError_t e = hipMalloc((void**)&p->tables, host.size() * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&p->scratch, frame_tmp * p->scratch_frames);
+    if (e == hipSuccess) e = hipMemcpy(p->tables, host.data(), host.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        const int code = e == hipErrorOutOfMemory ? CRTFX_E_NOMEM : CRTFX_E_HIP;
+        fail(nullptr, code, "crtfx_ingest_create: %s", hipGetErrorString(e));
+        if (p->tables) (void)hipFree(p->tables);
+        if (p->scratch) (void)hipFree(p->scratch);
+        delete p;
+        return code;
+    }
+    int32_t* t = p->tables;
+    p->x.min = t; t += dst_w; p->x.count = t; t += dst_w; p->x.k = t; t += (size_t)dst_w * x_ksize; p->x.ksize = x_ksize;
+    p->y.min = t; t += dst_h; p->y.count = t; t += dst_h; p->y.k = t; p->y.ksize = y_ksize;
+    note_plan(p, 0);
+    *out_plan = p;
+    return CRTFX_OK;
+}
+
+int crtfx_ingest_destroy(crtfx_ingest* p) {
+    if (!p) return CRTFX_OK;
+    DeviceGuard guard(p->device);
+    (void)hipDeviceSynchronize();
+    if (p->tables) (void)hipFree(p->tables);
+    if (p->scratch) (void)hipFree(p->scratch);
+    delete p;
+    return CRTFX_OK;
+}
+
+int crtfx_ingest_set_option(crtfx_ingest* p, int option, int value) {
+    if (!p) return CRTFX_E_INVALID;
+    if (option != CRTFX_INGEST_OPT_FORCE_GENERAL) return fail(p, CRTFX_E_INVALID, "unknown ingest option %d", option);
+    if (value != 0 && value != 1) return fail(p, CRTFX_E_INVALID, "FORCE_GENERAL takes 0 or 1, got %d", value);
+    p->force_general = value != 0;
+    note_plan(p, 0);
+    return CRTFX_OK;
+}
+
+int crtfx_ingest_last_plan(crtfx_ingest* p, char* buf, size_t n) {
+    if (!p || !buf || n == 0) return CRTFX_E_INVALID;
+    snprintf(buf, n, "%s", p->plan);
+    return CRTFX_OK;
+}
+
+int crtfx_ingest_run(crtfx_ingest* p, const void* src_base, size_t src_stride_bytes, void* dst_base, size_t dst_stride_bytes, int n, void* stream) {
+    if (!p) return CRTFX_E_INVALID;
+    if (!src_base || !dst_base) return fail(p, CRTFX_E_INVALID, "null frame pointer");
+    if (n < 1) return fail(p, CRTFX_E_INVALID, "n = %d frames", n);
+    const size_t src_bytes = (size_t)p->sh * p->sw * 3, dst_bytes = (size_t)p->dh * p->dw * 3;
+    if (n > 1 && (src_stride_bytes < src_bytes || dst_stride_bytes < dst_bytes))
+        return fail(p, CRTFX_E_INVALID, "frame strides %zu / %zu bytes are smaller than a frame (%zu / %zu)", src_stride_bytes, dst_stride_bytes, src_bytes, dst_bytes);
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) return fail(p, CRTFX_E_HIP, "hipGetDevice failed");
+    if (dev != p->device) return fail(p, CRTFX_E_INVALID, "current device %d is not the plan's device %d (call hipSetDevice first)", dev, p->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint8_t* src = static_cast<const uint8_t*>(src_base);
+    uint8_t* dst = static_cast<uint8_t*>(dst_base);
+    const bool fused = p->fused_fits && !p->force_general;
+    const int group = fused ? 32768 : p->scratch_frames;          // grid.z; the general path's scratch
+    for (int f = 0; f < n; f += group) {
+        const int g = n - f < group ? n - f : group;
+        if (fused) {
+            Args a = p->fused;
+            a.x = p->x; a.y = p->y;
+            a.src = src + (size_t)f * src_stride_bytes; a.src_stride = src_stride_bytes;
+            a.dst = dst + (size_t)f * dst_stride_bytes; a.dst_stride = dst_stride_bytes;
+            dim3 grid((p->dw + a.TW - 1) / a.TW, (p->dh + a.TH - 1) / a.TH, g);
+            hipLaunchKernelGGL(k_ingest_fused, grid, dim3(BLOCK), (size_t)p->lds_bytes, st, a);
+        } else {
+            hipLaunchKernelGGL(k_ingest_h, dim3((p->dw + BLOCK - 1) / BLOCK, p->sh, g), dim3(BLOCK), 0, st,
+                               src + (size_t)f * src_stride_bytes, src_stride_bytes, p->scratch, p->sh, p->sw, p->dw, p->x);
+            hipLaunchKernelGGL(k_ingest_v, dim3((p->dw * 3 + BLOCK - 1) / BLOCK, p->dh, g), dim3(BLOCK), 0, st,
+                               p->scratch, dst + (size_t)f * dst_stride_bytes, dst_stride_bytes, p->sh, p->dw, p->y);
+        }
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(p, CRTFX_E_HIP, "ingest launch: %s", hipGetErrorString(e));
+    }
+    note_plan(p, n);
+    return CRTFX_OK;
+}
+
+}  // extern "C"

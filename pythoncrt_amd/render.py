@@ -7,7 +7,8 @@ ref:1034), the writer call it already makes (`writer.write_frame`, ref:1101) and
     n = pythoncrt_amd.process_frames(frame_iter, writer.write_frame, out_w, out_h, fps_out, total_frames,
                                      scanline_strength=scanline_strength, triad_strength=triad_strength, ..., progress_cb=progress_cb)
 
-What it keeps of the reference's loop: frames of another size are resized with Pillow's BILINEAR first (ref:1039-1041); frame i runs at
+What it keeps of the reference's loop: frames of another size are resized as Pillow's BILINEAR does first (ref:1039-1041; on the device,
+byte for byte Pillow's result — pythoncrt_amd.ingest — or with Pillow itself under `resize_on="host"`); frame i runs at
 phase = i / fps * scanline_speed_px_s and time_sec = i / fps (ref:1043, :1064); frames are committed strictly in order, frame 0 passes through
 unblended, frame i > 0 blends with the state frame i - 1 left (ref:1086-1096); `progress_cb(min(1, frames_written / total_frames))` after
 every frame (ref:1104-1105); the text overlay is rasterised once (ref:1076-1077 builds the same plane for every frame).  What differs: the
@@ -54,7 +55,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                    grain_size: int = 1, scanline_angle: float = 0.0, scanline_thickness: float = 1.0, warp_strength: float = 0.0,
                    text: str = "", text_font: str = "", text_size: int = 36, text_color: str = "#FFFFFF", text_pos: Tuple[int, int] = (32, 32),
                    text_after: bool = True, progress_cb: Optional[Callable[[float], None]] = None,
-                   batch: int = 16, noise_seed: Optional[int] = None, device=None, **io_keywords) -> int:
+                   batch: int = 16, noise_seed: Optional[int] = None, device=None, resize_on: str = "device", **io_keywords) -> int:
     """Render every frame of `frame_iter` (H x W x 3 uint8 RGB arrays) and hand the finished uint8 frames to `write_frame` in order.
     Effect keywords: the names, meaning and defaults of process_video / the CLI (ref:864-911, :1155-1206); the caller applies the clamps of
     ref:1225-1266 as the reference's `main` does (`pythoncrt_amd.cli.settings_from_args` restates them).  Returns the number of frames written.
@@ -62,6 +63,10 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     reference's `FFMPEG_VideoWriter.write_frame` writes it to the encoder's pipe at once).
     `progress_cb(fraction)` is called after every written frame with min(1, written / total_frames) (ref:1104-1105; the reference always knows
     its total, ref:1029).  With `total_frames=None` no fraction can be formed: the callback is then called ONCE, with 1.0, after the last frame.
+    Frames of another size than out_h x out_w are brought to it as `Image.resize((out_w, out_h), Image.BILINEAR)` does (ref:1039-1041):
+    with `resize_on="device"` (default) they are uploaded at their own size and resized by the ingest kernels (IngestResize: Pillow's bytes),
+    a batch ending early where the source size changes; with `resize_on="host"` by Pillow itself on the calling thread, the reference's
+    literal form (kept for A/B).  Both give the same bytes.
     If `frame_iter` or `write_frame` raises, the GPU work already queued is drained (device synchronize) before the exception leaves this
     function, so that the staging buffers are not freed under a running copy."""
     import os
@@ -70,6 +75,8 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     unknown = set(io_keywords) - set(_IO_KEYS)
     if unknown:
         raise TypeError(f"process_frames() got unexpected keyword arguments {sorted(unknown)}")
+    if resize_on not in ("device", "host"):
+        raise ValueError(f"resize_on must be 'device' or 'host', got {resize_on!r}")
     if not torch.cuda.is_available():
         raise RuntimeError("no ROCm device visible; pythoncrt_amd has no CPU fallback")
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -107,14 +114,42 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     state, index, written, k = None, 0, 0, 0
     pending = None                   # (slot, frames, download event) of the batch whose frames are still to be written
 
+    MAX_SOURCES = 4                  # source sizes whose staging buffers and ingest plan are kept
+    sources = {}                     # (src_h, src_w) -> _Source, in order of last use
+    carry = None                     # a frame already taken from the iterator that starts the next batch (its source size differs)
+
+    class _Source:
+        """Staging of one off-size source: pinned and device slots of ITS size, the plan that resizes them into dev_in[d]."""
+        def __init__(self, sh, sw):
+            from .ingest import IngestResize
+            self.plan = IngestResize(dev, (sh, sw), (h, w))
+            self.pin = [torch.empty((B, sh, sw, 3), dtype=torch.uint8).pin_memory() for _ in range(NS)]
+            self.dev = [torch.empty((B, sh, sw, 3), dtype=torch.uint8, device=dev) for _ in range(NS)]
+            self.np = [t.numpy() for t in self.pin]
+            self.up_done = [None] * NS           # the upload that last read pin[d]
+            self.kernels_done = [None] * NS      # the resize that last read dev[d]
+
+    def source(key):
+        src = sources.pop(key, None)
+        if src is None:
+            if len(sources) >= MAX_SOURCES:      # rare: drop the least recently used size once its queued work is done
+                torch.cuda.synchronize(dev)
+                sources.pop(next(iter(sources)))
+            src = _Source(*key)
+        sources[key] = src
+        return src
+
     def fit(frame):
+        """(array to stage, None) for a frame at the output size or resized on the host; (array, (src_h, src_w)) for one the device resizes."""
         a = np.asarray(frame)
         if a.ndim != 3 or a.shape[2] != 3:
             raise ValueError(f"frames must be H x W x 3 RGB arrays, got {a.shape}")
         if a.shape[0] != h or a.shape[1] != w:                                  # ref:1039-1041
+            if resize_on == "device":
+                return a, (int(a.shape[0]), int(a.shape[1]))
             from PIL import Image
             a = np.asarray(Image.fromarray(np.ascontiguousarray(a, dtype=np.uint8)).resize((w, h), Image.BILINEAR))
-        return a
+        return a, None
 
     def drain(p):
         nonlocal written
@@ -133,30 +168,58 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
             d = k % NS
             if up_done[d] is not None:
                 up_done[d].synchronize()             # the upload that read this pinned slot two batches ago (long done)
-            n = 0
+            n, key, src, slot = 0, None, None, np_in[d]
             while n < B:
-                try:
-                    frame = next(it)
-                except StopIteration:
-                    done = True
+                if carry is not None:
+                    (a, akey), carry = carry, None
+                else:
+                    try:
+                        frame = next(it)
+                    except StopIteration:
+                        done = True
+                        break
+                    a, akey = fit(frame)
+                if n == 0:
+                    key = akey
+                    if key is not None:                  # an off-size batch is staged at ITS size
+                        src = source(key)
+                        if src.up_done[d] is not None:
+                            src.up_done[d].synchronize()
+                        slot = src.np[d]
+                elif akey != key:                        # the source size changes: this frame opens the next batch
+                    carry = (a, akey)
                     break
-                np.copyto(np_in[d][n], fit(frame), casting="unsafe")
+                np.copyto(slot[n], a, casting="unsafe")
                 n += 1
             if n:
-                if kernels_done[d] is not None:
-                    s_up.wait_event(kernels_done[d])
-                with torch.cuda.stream(s_up):
-                    dev_in[d][:n].copy_(pin_in[d][:n], non_blocking=True)
-                    up = torch.cuda.Event()
-                    up.record(s_up)
-                up_done[d] = up
-                compute.wait_event(up)
+                if src is None:
+                    if kernels_done[d] is not None:
+                        s_up.wait_event(kernels_done[d])
+                    with torch.cuda.stream(s_up):
+                        dev_in[d][:n].copy_(pin_in[d][:n], non_blocking=True)
+                        up = torch.cuda.Event()
+                        up.record(s_up)
+                    up_done[d] = up
+                    compute.wait_event(up)
+                else:
+                    if src.kernels_done[d] is not None:
+                        s_up.wait_event(src.kernels_done[d])
+                    with torch.cuda.stream(s_up):
+                        src.dev[d][:n].copy_(src.pin[d][:n], non_blocking=True)
+                        up = torch.cuda.Event()
+                        up.record(s_up)
+                    src.up_done[d] = up
+                    compute.wait_event(up)
+                    # dev_in[d]: its last upload (two batches ago) was awaited by `compute` then, its last readers ran on `compute`
+                    src.plan.run(src.dev[d][:n], out=dev_in[d][:n])                  # ref:1039-1041, on the compute stream
                 if down_done[d] is not None:
                     compute.wait_event(down_done[d])
                 _, state = pipe.run(dev_in[d][:n], first_index=index, state=state, out=dev_out[d][:n])
                 kd = torch.cuda.Event()
                 kd.record(compute)
                 kernels_done[d] = kd
+                if src is not None:
+                    src.kernels_done[d] = kd
                 # pin_out[d] was drained one iteration ago (drain below runs before the next batch is enqueued into the same slot)
                 s_down.wait_event(kd)
                 with torch.cuda.stream(s_down):

@@ -254,5 +254,31 @@ def glitch_offsets_preview(h2: int, w2: int, scanline_phase_px: float, glitch_am
     return y0, np.ascontiguousarray(np.rint(offs_row).astype(np.int32)[:, None])
 
 
+def pil_resample_axis(n_in: int, n_out: int):
+    """One axis of Pillow's 8-bit BILINEAR resampler (`Image.resize(..., Image.BILINEAR)`, ref:1039-1041; Pillow's
+    src/libImaging/Resample.c, precompute_coeffs + normalize_coeffs_8bpc) as integer tables for crtfx_ingest_create:
+    (xmin int32[n_out], count int32[n_out], k int32[n_out, ksize]).  Output sample xx of a pass is
+    clamp((2**21 + sum(k[xx, t] * sample[xmin[xx] + t] for t < count[xx])) >> 22, 0, 255).  Every expression is
+    evaluated in float64 in Pillow's order of operations (the weights are summed in tap order), so the integers are Pillow's own."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"pil_resample_axis({n_in}, {n_out})")
+    scale = np.float64(n_in) / np.float64(n_out)
+    fs = max(scale, np.float64(1.0))
+    support = np.float64(1.0) * fs                                # the triangle filter's support is 1.0
+    ksize = int(np.ceil(support)) * 2 + 1
+    ss = np.float64(1.0) / fs
+    center = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)                 # astype truncates as the C cast does
+    count = np.minimum((center + support + 0.5).astype(np.int64), n_in) - xmin
+    x = np.arange(ksize, dtype=np.int64)[None, :]
+    a = np.abs(((x + xmin[:, None]).astype(np.float64) - center[:, None] + 0.5) * ss)
+    w = np.where((a < 1.0) & (x < count[:, None]), 1.0 - a, 0.0)
+    ww = np.add.accumulate(w, axis=1)[:, -1:]                     # sequential, in tap order (the zeros behind `count` add nothing)
+    w = np.divide(w, ww, out=w.copy(), where=ww != 0.0)
+    k = (0.5 + w * np.float64(1 << 22)).astype(np.int32)          # PRECISION_BITS = 32 - 8 - 2; the weights are non-negative
+    return np.ascontiguousarray(xmin.astype(np.int32)), np.ascontiguousarray(count.astype(np.int32)), np.ascontiguousarray(k)
+
+
 def ptr(a) -> int:
     return 0 if a is None else a.ctypes.data
