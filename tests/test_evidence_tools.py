@@ -259,6 +259,29 @@ def test_every_phosphor_build_has_a_gpu_sweep_row():
     assert not missing, f"rows of tests/radius_builds.BUILDS naming builds the library lacks: {missing}"
 
 
+def warp_inventory(lib_path):
+    """(k_warp_lean / k_warp instances in the library that no row of tests/warp_builds.ROWS names, instances a row names that the library lacks)."""
+    import kernel_resources
+    from tests import warp_builds
+    have = warp_builds.library_instances(kernel_resources.resources(lib_path))
+    want = warp_builds.covered_instances()
+    return sorted(have - want), sorted(want - have)
+
+
+def test_every_warp_build_has_a_gpu_sweep_row():
+    """Every crtfx::k_warp_lean<...> instance compiled into libcrtfx.so (24 general, six plain and two commit-only builds) and the general
+    crtfx::k_warp is named by a row of the table tests/test_warp_builds_gpu.py holds to the float32-storage model, and every row names an
+    instance the library has: an instantiation added to crtfx.hip fails here, on the CPU, until the GPU sweep reaches it."""
+    from pythoncrt_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build()
+    uncovered, missing = warp_inventory(_lib.LIB_PATH)
+    assert not uncovered, f"warp builds with no row in tests/warp_builds.ROWS: {uncovered}"
+    assert not missing, f"rows of tests/warp_builds.ROWS naming builds the library lacks: {missing}"
+    from tests import warp_builds
+    assert len(warp_builds.covered_instances()) == 33
+
+
 def test_phosphor_sf_words_come_from_the_sources():
     from tests import radius_builds
     w = radius_builds.sf_words()

@@ -19,6 +19,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 from oracle import crt_oracle as orc  # noqa: E402  (checker only)
+from tests import warp_model as wm  # noqa: E402  (the float32-storage model of the warp / commit stage: bit-exact bar)
 
 
 @pytest.fixture(scope="module")
@@ -59,6 +60,28 @@ def run_both(pc, frame, cfg, noise_plane=None, **kw):
     exp = orc.apply_static_effects(*pos(tm_o, vg_o), noise_plane=noise_plane, **kw)
     assert got.dtype == np.float32 and got.shape == frame.shape
     return got, exp
+
+
+def model_pre(frame, cfg, noise_plane=None):
+    """The pre-warp image as the GPU holds it (tests/warp_model.py): the oracle's chain of run_both stopped before the warp, narrowed to
+    float32, widened back to float64 when the chain is promoted."""
+    c = dict(BASE, **cfg)
+    h, w = frame.shape[:2]
+    tm = orc.make_triad_mask(h, w, *c["triad"]) if c["triad"] else None
+    vg = orc.make_vignette(h, w, c["vignette"]) if c["vignette"] else None
+    pre = orc.apply_static_effects(frame, c["scanline_strength"], tm, c["triad_gamma"], c["triad_preserve_luma"], c["aberration_px"],
+                                   c["bloom_sigma"], c["bloom_strength"], c["bloom_threshold"], c["noise_strength"], vg,
+                                   c["scanline_period_px"], c["scanline_phase_px"], c["fast_bloom"], c["pixel_size"], 0, 0.0,
+                                   noise_plane=noise_plane, stop_before_warp=True)
+    return pre.astype(np.float32).astype(pre.dtype)
+
+
+def assert_equals_model(got, exp, what="warped image"):
+    got, exp = np.asarray(got), np.asarray(exp)
+    assert got.dtype == exp.dtype and got.shape == exp.shape, (what, got.dtype, exp.dtype)
+    if not np.array_equal(got, exp):
+        bad = np.argwhere(got != exp)
+        raise AssertionError(f"{what}: {len(bad)} of {got.size} samples differ from the float32-storage model; first at {bad[0].tolist()}")
 
 
 def assert_bit_exact(got, exp):
@@ -302,6 +325,7 @@ def test_full_chain_with_warp(pc, hw, sigma):
     plane = np.random.default_rng(13).standard_normal((h, w), dtype=np.float32)
     got, exp = run_both(pc, frame, dict(FULL, bloom_sigma=sigma), noise_plane=plane, warp_strength=0.15)
     assert np.abs(got.astype(np.float64) - exp).max() <= 3e-7
+    assert_equals_model(got, wm.static_image(model_pre(frame, dict(FULL, bloom_sigma=sigma), plane), 0.15))
     # without the warp the same chain is bit-exact
     got, exp = run_both(pc, frame, dict(FULL, bloom_sigma=sigma), noise_plane=plane)
     assert_bit_exact(got, exp)
@@ -320,12 +344,15 @@ def test_apply_crt_effect_sequence(pc, warp):
     c = dict(BASE, **FULL)
     tm_g, tm_o = pc.make_triad_mask(h, w, 0.35, 0.5), orc.make_triad_mask(h, w, 0.35, 0.5)
     vg_g, vg_o = pc.make_vignette(h, w, 0.25), orc.make_vignette(h, w, 0.25)
-    sg = so = None
+    sg = so = sm = None
     for i in range(4):
         frame = make_frame(h, w, seed=20 + i, kind="grad")
         plane = np.random.default_rng(30 + i).standard_normal((h, w), dtype=np.float32)
         ug, sg = pc.apply_crt_effect(*crt_args(frame, tm_g, vg_g, 0.5, sg, float(i), c), warp_strength=warp, noise_plane=plane)
         uo, so = orc.apply_crt_effect(*crt_args(frame, tm_o, vg_o, 0.5, so, float(i), c), warp_strength=warp, noise_plane=plane)
+        um, sm = wm.preview_step(wm.warp(model_pre(frame, dict(FULL, scanline_phase_px=float(i)), plane), warp), 0.5, sm)
+        assert_equals_model(ug, um, f"tick {i} frame")
+        assert_equals_model(sg, sm, f"tick {i} state")
         assert ug.dtype == np.uint8 and sg.dtype == np.float32
         assert np.abs(sg.astype(np.float64) - so).max() <= 4e-7
         d = np.abs(ug.astype(np.int16) - uo.astype(np.int16))
@@ -454,6 +481,7 @@ def test_1080p_frame_against_oracle(pc):
     assert_bit_exact(got, exp)
     gotw, expw = run_both(pc, frame, FULL, noise_plane=plane, warp_strength=0.15)
     assert np.abs(gotw.astype(np.float64) - expw).max() <= 3e-7
+    assert_equals_model(gotw, wm.static_image(model_pre(frame, FULL, plane), 0.15))
     d = np.abs(orc.convert_scale_abs(gotw).astype(np.int16) - orc.convert_scale_abs(expw).astype(np.int16))
     assert d.max() <= 1 and (d != 0).mean() < 1e-3
 
@@ -1147,6 +1175,10 @@ def test_4k_render_loop_against_oracle(pc):
                                 rs.vignette_strength, noise_planes=planes, first_index=first)
     d = np.abs(out.cpu().numpy().astype(np.int16) - np.stack(exp).astype(np.int16))
     assert d.max() <= 1 and (d != 0).mean() < 1e-3, (int(d.max()), float((d != 0).mean()))
+    # ... and, fed with the same grain planes, the float32-storage model of the warp and the commit: equality
+    cfg = dict(wm.OFF, **{k: getattr(rs, k) for k in wm.OFF})
+    m_out, _ = wm.render(list(frames), cfg, first=first, planes=planes)
+    assert_equals_model(out.cpu().numpy(), np.stack(m_out), "4K frames")
 
 
 @pytest.mark.parametrize("sigma,warp", [(11.0, 0.15), (45.0, 0.15), (3.0, 0.0), (1.2, 0.0), (11.0, 0.0)])          # radii 33, 135 | 9, 4, 33 with the commit-only k_warp_lean
