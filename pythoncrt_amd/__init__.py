@@ -3,13 +3,15 @@
     from pythoncrt_amd import apply_crt_effect, apply_static_effects, make_triad_mask, make_vignette
     from pythoncrt_amd import process_frames      # the loop of process_video (ref:1037-1131) over the caller's frame iterator and writer
     from pythoncrt_amd import IngestResize        # its first step (ref:1039-1041) on the device: Pillow's BILINEAR resize of uint8 frames
+    from pythoncrt_amd import EgressYuv           # its last step (ref:970-1002, `-pix_fmt yuv420p`) on the device: rgb24 -> yuv420p / nv12
 
 See DESIGN.md (path, kernels, roofline) and INTEGRATION.md (how the reference binds to it).
 """
 from .effects import (DeviceState, TriadMask, VignetteMask, apply_crt_effect, apply_static_effects, make_triad_mask,
                       make_vignette)
+from .egress import EgressYuv
 from .ingest import IngestResize
 from .render import iter_rgb24, process_frames
 
 __all__ = ["DeviceState", "TriadMask", "VignetteMask", "apply_crt_effect", "apply_static_effects", "make_triad_mask", "make_vignette",
-           "process_frames", "iter_rgb24", "IngestResize"]
+           "process_frames", "iter_rgb24", "IngestResize", "EgressYuv"]

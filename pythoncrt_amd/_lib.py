@@ -13,8 +13,9 @@ ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("CRTFX_LIB") or os.path.join(_HERE, "libcrtfx.so")   # CRTFX_LIB: dev A/B builds only
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = [os.path.join(CSRC, f) for f in ("crtfx.hip", "crtfx_rr.hip", "crtfx_kernels.hip.h", "crtfx_common.hip.h", "crtfx_blur.hip.h", "crtfx_point.hip.h",
-                                                "crtfx_phosphor.hip.h", "crtfx_phosphor_ct.hip.h", "crtfx_warp.hip.h", "crtfx_internal.h", "crtfx_ingest.hip")] + \
-          [os.path.join(ROOT, "include", "crtfx.h"), os.path.join(ROOT, "include", "crtfx_ingest.h")]
+                                                "crtfx_phosphor.hip.h", "crtfx_phosphor_ct.hip.h", "crtfx_warp.hip.h", "crtfx_internal.h", "crtfx_ingest.hip",
+                                                "crtfx_egress.hip")] + \
+          [os.path.join(ROOT, "include", f) for f in ("crtfx.h", "crtfx_ingest.h", "crtfx_egress.h")]
 RR_RADII = tuple(range(1, 31))      # one register-window build per radius up to 30 (crtfx_internal.h); larger radii: the split path
 
 OK, E_INVALID, E_HIP, E_UNSUPPORTED, E_NOMEM = 0, -1, -2, -3, -4
@@ -99,6 +100,19 @@ INGEST_SYMBOLS = {
     "crtfx_ingest_last_plan": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t]),
 }
 
+# ... and every symbol include/crtfx_egress.h declares (the egress stage: a handle of its own, pythoncrt_amd/egress.py)
+EGRESS_YUV420P, EGRESS_NV12 = 0, 1
+EGRESS_OPT_FORCE_GENERAL = 1
+EGRESS_SYMBOLS = {
+    "crtfx_egress_create": (ctypes.c_int, [ctypes.c_int] * 5 + [_vp, _vp, ctypes.POINTER(_vp)]),
+    "crtfx_egress_destroy": (ctypes.c_int, [_vp]),
+    "crtfx_egress_last_error": (ctypes.c_char_p, [_vp]),
+    "crtfx_egress_frame_bytes": (ctypes.c_size_t, [_vp]),
+    "crtfx_egress_run": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
+    "crtfx_egress_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
+    "crtfx_egress_last_plan": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t]),
+}
+
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC"]
 
 
@@ -118,6 +132,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), out: str =
         jobs.append([hipcc, *HIPCC_FLAGS, *extra_flags, *inc, f"-DRR_R={r}", "-c", os.path.join(CSRC, "crtfx_rr.hip"),
                      "-o", os.path.join(objdir, f"crtfx_rr_{r}.o")])
     jobs.append([hipcc, *HIPCC_FLAGS, *extra_flags, *inc, "-c", os.path.join(CSRC, "crtfx_ingest.hip"), "-o", os.path.join(objdir, "crtfx_ingest.o")])
+    jobs.append([hipcc, *HIPCC_FLAGS, *extra_flags, *inc, "-c", os.path.join(CSRC, "crtfx_egress.hip"), "-o", os.path.join(objdir, "crtfx_egress.o")])
 
     def run(cmd):
         if verbose:
@@ -153,7 +168,8 @@ def build_variant(name: str, extra_flags, radii=(9,), main_tu: bool = False) -> 
         main = os.path.join(objdir, "crtfx.o")
         subprocess.run([hipcc, *HIPCC_FLAGS, *extra_flags, *inc, "-c", os.path.join(CSRC, "crtfx.hip"), "-o", main], check=True)
     out = os.path.join(ROOT, "build", "ab", f"libcrtfx_{name}.so")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out, main, *objs, os.path.join(base, "crtfx_ingest.o")], check=True)
+    subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out, main, *objs, os.path.join(base, "crtfx_ingest.o"),
+                    os.path.join(base, "crtfx_egress.o")], check=True)
     return out
 
 
@@ -176,7 +192,7 @@ def load() -> ctypes.CDLL:
             "`python -c 'import __graft_entry__ as g; g.build()'` (or pythoncrt_amd._lib.build()). "
             "pythoncrt_amd has no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in {**SYMBOLS, **INGEST_SYMBOLS}.items():
+    for name, (res, args) in {**SYMBOLS, **INGEST_SYMBOLS, **EGRESS_SYMBOLS}.items():
         fn = getattr(lib, name)   # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

@@ -12,6 +12,13 @@ pipe), from a file or stdin/stdout, so the drop-in sits between two ffmpeg proce
       python -m pythoncrt_amd.cli --input - --width 1920 --height 1080 --fps 30 --output - [effect flags] |
       ffmpeg -f rawvideo -pix_fmt rgb24 -s 1920x1080 -r 30 -i - out.mp4
 
+With `--out-pix-fmt yuv420p` (or `nv12`; `--out-matrix bt601|bt709`, `--out-range tv|pc`) the finished frames are converted to the
+encoder's 4:2:0 format on the GPU (include/crtfx_egress.h) and leave as 1.5 bytes per pixel instead of 3 — half the download, half the
+pipe, and no conversion left for the encoder:
+
+      python -m pythoncrt_amd.cli --input - --width 1920 --height 1080 --fps 30 --output - --out-pix-fmt yuv420p [effect flags] |
+      ffmpeg -f rawvideo -pix_fmt yuv420p -s 1920x1080 -r 30 -i - out.mp4
+
 `--gui`, `--gpu`, `--nvenc-preset`, `--encoder`, `--decoder`, `--crf` and `--bitrate` are accepted for
 compatibility and ignored (encode/decode/UI are not part of this path).  `--text*` rasterise the overlay on
 the host with Pillow (ref:366-414) and alpha-blend it on the GPU before or after the effects.
@@ -99,6 +106,19 @@ def build_parser() -> argparse.ArgumentParser:
                    help="regular files: through pinned staging slots (staged, the default: at the PCIe rate on a disk-backed filesystem), DMA "
                         "straight from / into the registered file mapping (mapped: measured slower on this platform, profiles/r05_cli_throughput.txt), "
                         "or mapped where the first batch shows it is faster (auto)")
+    return p
+
+
+OUT_PIX_FMTS = ("rgb24", "yuv420p", "nv12")
+
+
+def add_output_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
+    """The output-format flags of `main` (not in the reference, whose encoder pipe is always rgb24 in and `-pix_fmt yuv420p` out, ref:970-1002).
+    Kept out of `build_parser`, which restates the reference's schema plus the four additions listed there."""
+    p.add_argument("--out-pix-fmt", type=str, default="rgb24", choices=list(OUT_PIX_FMTS),
+                   help="format of the frames written: raw rgb24 (default), or planar yuv420p / semi-planar nv12 converted on the GPU (1.5 bytes per pixel)")
+    p.add_argument("--out-matrix", type=str, default="bt601", choices=["bt601", "bt709"], help="yuv420p / nv12: the RGB -> Y'CbCr matrix")
+    p.add_argument("--out-range", type=str, default="tv", choices=["tv", "pc"], help="yuv420p / nv12: limited (tv, 16-235) or full (pc) range")
     return p
 
 
@@ -807,6 +827,10 @@ def main_sharded(a, rank: int, world: int) -> int:
     the clip's chunks of --batch frames are dealt round-robin over the ranks, each rank reads its chunks
     from the raw input file and writes them at the same offsets of the output file; with --persistence > 0 one
     float32 state frame per chunk boundary travels to the next rank (RCCL)."""
+    if getattr(a, "out_pix_fmt", "rgb24") != "rgb24":
+        # every rank writes its chunks at offsets of its own: those, and the downloads behind them, are rgb24-sized here
+        raise SystemExit(f"--out-pix-fmt {a.out_pix_fmt} is not supported by the sharded CLI (one process per GPU writes rgb24 only); "
+                         "run one process, or convert behind it")
     import os
     import torch
     import torch.distributed as dist
@@ -934,7 +958,7 @@ def main_sharded(a, rank: int, world: int) -> int:
 
 
 def main(argv=None) -> int:
-    a = build_parser().parse_args(argv)
+    a = add_output_flags(build_parser()).parse_args(argv)
     import os as _os
     if int(_os.environ.get("WORLD_SIZE", "1")) > 1 or _os.environ.get("CRTFX_FORCE_DIST") == "1":
         if a.gui or not a.input or a.width <= 0 or a.height <= 0:
@@ -964,6 +988,14 @@ def main(argv=None) -> int:
     out_path = a.output if a.output else (a.input + "_crt.rgb" if a.input != "-" else "-")
     B = max(1, int(a.batch))
     frame_bytes = h * w * 3
+    # --out-pix-fmt yuv420p / nv12: the chain's frames are converted on the device behind it (EgressYuv) and everything downstream — the device
+    # and pinned output slots, the download, the output file's offsets and size — is in frames of out_bytes instead of frame_bytes
+    egress = None
+    if a.out_pix_fmt != "rgb24":
+        from .egress import EgressYuv
+        egress = EgressYuv(dev, (h, w), layout=a.out_pix_fmt, matrix=a.out_matrix, range=a.out_range)
+    out_bytes = frame_bytes if egress is None else egress.frame_bytes
+    out_shape = (B, h, w, 3) if egress is None else (B, out_bytes)
     t0 = time.perf_counter()
     # regular files: positional I/O on a few threads (a pipe / the terminal: the plain sequential calls)
     in_pos = _seekable(fin) and a.input != "-"
@@ -984,9 +1016,9 @@ def main(argv=None) -> int:
     out_plan = None
     if in_pos and out_pos:
         n_total = os.fstat(fin.fileno()).st_size // frame_bytes
-        out_plan = [(k * B * frame_bytes, min(B, n_total - k * B) * frame_bytes) for k in range((n_total + B - 1) // B)] or None
+        out_plan = [(k * B * out_bytes, min(B, n_total - k * B) * out_bytes) for k in range((n_total + B - 1) // B)] or None
         if presize and out_pos:
-            os.ftruncate(fout.fileno(), n_total * frame_bytes)
+            os.ftruncate(fout.fileno(), n_total * out_bytes)
 
     def jobs():                                                     # whole batches until the stream ends (the reader stops at a short read)
         off = 0
@@ -995,12 +1027,13 @@ def main(argv=None) -> int:
             off += B * frame_bytes
     NS = 3
     reader = _Reader(fin, in_pos, jobs(), (B, h, w, 3), frame_bytes, slots=NS, io=a.io, autostart=False)
-    writer = _Writer(fout, out_pos, (B, h, w, 3), frame_bytes, slots=NS, plan=out_plan, io=a.io)
+    writer = _Writer(fout, out_pos, out_shape, out_bytes, slots=NS, plan=out_plan, io=a.io)
     t_pipe = time.perf_counter()                                    # the pipeline proper: first read issued ... last batch written (the --staging-report line)
     t_slots = t_pipe - t_start - t_imports - t_engine
     reader.start()
     dev_in = [torch.empty((B, h, w, 3), dtype=torch.uint8, device=dev) for _ in range(NS)]
     dev_out = [torch.empty((B, h, w, 3), dtype=torch.uint8, device=dev) for _ in range(NS)]
+    dev_send = dev_out if egress is None else [torch.empty(out_shape, dtype=torch.uint8, device=dev) for _ in range(NS)]      # what is downloaded
     compute = torch.cuda.current_stream(dev)
     s_up, s_down = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
     kernels_done = [None] * NS                                      # per device slot: its batch's kernels have finished (dev_in free again)
@@ -1035,6 +1068,8 @@ def main(argv=None) -> int:
                 if tim:
                     k0 = torch.cuda.Event(enable_timing=True); k0.record(compute)
                 _, state = pipe.run(dev_in[d][:n], first_index=index, state=state, out=dev_out[d][:n])
+                if egress is not None:                            # on the compute stream, behind the chain: counted with the kernels below
+                    egress.run(dev_out[d][:n], out=dev_send[d][:n])
                 kd = torch.cuda.Event(enable_timing=tim)
                 kd.record(compute)
                 kernels_done[d] = kd
@@ -1047,14 +1082,14 @@ def main(argv=None) -> int:
                 s_down.wait_event(kd)
                 if tim:
                     d0 = torch.cuda.Event(enable_timing=True); d0.record(s_down)
-                writer.download(j, n, dev_out[d], s_down)         # into the pinned slot, or straight into the registered output mapping
+                writer.download(j, n, dev_send[d], s_down)        # into the pinned slot, or straight into the registered output mapping
                 dn = torch.cuda.Event(enable_timing=tim)
                 dn.record(s_down)
                 down_done[d] = dn
                 if tim:
                     marks.append((u0, up, k0, kd, d0, dn, n))
                 writer.put(j, n, dn, out_off if out_pos else None)
-                out_off += n * frame_bytes
+                out_off += n * out_bytes
             # a pinned input slot goes back to the reader once its upload has completed: the PREVIOUS batch's is waited for here (long done),
             # so this thread never sits on the upload it has just enqueued
             t_enq += time.perf_counter() - tt
@@ -1094,7 +1129,7 @@ def main(argv=None) -> int:
         if out_pos:
             try:
                 fout.flush()
-                os.ftruncate(fout.fileno(), min(int(writer.frames), index) * frame_bytes)
+                os.ftruncate(fout.fileno(), min(int(writer.frames), index) * out_bytes)
             except OSError:
                 pass
         raise
@@ -1102,7 +1137,7 @@ def main(argv=None) -> int:
     reader.close()
     fout.flush()
     if out_pos:
-        os.ftruncate(fout.fileno(), index * frame_bytes)      # an input that ended before its planned length, an output file that was longer
+        os.ftruncate(fout.fileno(), index * out_bytes)        # an input that ended before its planned length, an output file that was longer
     if fout is not sys.stdout.buffer:
         fout.close()
     if fin is not sys.stdin.buffer:
@@ -1116,8 +1151,9 @@ def main(argv=None) -> int:
         dn_ms = sum(m[4].elapsed_time(m[5]) for m in mk) / len(mk)
         span = mk[0][0].elapsed_time(mk[-1][5]) / len(mk)
         nb = sum(m[6] for m in mk) / len(mk) * frame_bytes
+        nb_out = nb / frame_bytes * out_bytes
         print(f"staging (GPU side, per batch of {nb / frame_bytes:.0f} frames): upload {up_ms:.2f} ms = {nb / up_ms / 1e6:.1f} GB/s, kernels {k_ms:.2f} ms, "
-              f"download {dn_ms:.2f} ms = {nb / dn_ms / 1e6:.1f} GB/s; one batch every {span:.2f} ms = {nb / frame_bytes / span * 1e3:.0f} frames/s", file=sys.stderr)
+              f"download {dn_ms:.2f} ms = {nb_out / dn_ms / 1e6:.1f} GB/s; one batch every {span:.2f} ms = {nb / frame_bytes / span * 1e3:.0f} frames/s", file=sys.stderr)
     if a.staging_report:
         # start-up (imports, ctx, tables, pinning the staging slots) and the exit are outside this figure; the reader's first read, the unoverlapped
         # legs of the first and last batch and the output's last write are inside it

@@ -55,7 +55,8 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                    grain_size: int = 1, scanline_angle: float = 0.0, scanline_thickness: float = 1.0, warp_strength: float = 0.0,
                    text: str = "", text_font: str = "", text_size: int = 36, text_color: str = "#FFFFFF", text_pos: Tuple[int, int] = (32, 32),
                    text_after: bool = True, progress_cb: Optional[Callable[[float], None]] = None,
-                   batch: int = 16, noise_seed: Optional[int] = None, device=None, resize_on: str = "device", **io_keywords) -> int:
+                   batch: int = 16, noise_seed: Optional[int] = None, device=None, resize_on: str = "device",
+                   out_pix_fmt: str = "rgb24", out_matrix: str = "bt601", out_range: str = "tv", **io_keywords) -> int:
     """Render every frame of `frame_iter` (H x W x 3 uint8 RGB arrays) and hand the finished uint8 frames to `write_frame` in order.
     Effect keywords: the names, meaning and defaults of process_video / the CLI (ref:864-911, :1155-1206); the caller applies the clamps of
     ref:1225-1266 as the reference's `main` does (`pythoncrt_amd.cli.settings_from_args` restates them).  Returns the number of frames written.
@@ -67,6 +68,10 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     with `resize_on="device"` (default) they are uploaded at their own size and resized by the ingest kernels (IngestResize: Pillow's bytes),
     a batch ending early where the source size changes; with `resize_on="host"` by Pillow itself on the calling thread, the reference's
     literal form (kept for A/B).  Both give the same bytes.
+    `out_pix_fmt="yuv420p"` / `"nv12"` hands the writer the encoder's format instead of rgb24 (the reference's encoder branches all end in
+    `-pix_fmt yuv420p`, ref:970-1002): the finished frames are converted on the device behind the chain (EgressYuv, include/crtfx_egress.h:
+    `out_matrix` "bt601" / "bt709", `out_range` "tv" / "pc"), only frame_bytes = h * w + 2 * ceil(h / 2) * ceil(w / 2) bytes per frame are
+    downloaded, and `write_frame` receives a 1-D uint8 array of that many bytes.  "rgb24" (default) is the path as it was.
     If `frame_iter` or `write_frame` raises, the GPU work already queued is drained (device synchronize) before the exception leaves this
     function, so that the staging buffers are not freed under a running copy."""
     import os
@@ -77,6 +82,8 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         raise TypeError(f"process_frames() got unexpected keyword arguments {sorted(unknown)}")
     if resize_on not in ("device", "host"):
         raise ValueError(f"resize_on must be 'device' or 'host', got {resize_on!r}")
+    if out_pix_fmt not in ("rgb24", "yuv420p", "nv12"):
+        raise ValueError(f"out_pix_fmt must be 'rgb24', 'yuv420p' or 'nv12', got {out_pix_fmt!r}")
     if not torch.cuda.is_available():
         raise RuntimeError("no ROCm device visible; pythoncrt_amd has no CPU fallback")
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -101,9 +108,15 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
 
     NS = 2
     pin_in = [torch.empty((B, h, w, 3), dtype=torch.uint8).pin_memory() for _ in range(NS)]
-    pin_out = [torch.empty((B, h, w, 3), dtype=torch.uint8).pin_memory() for _ in range(NS)]
+    egress = None
+    if out_pix_fmt != "rgb24":                                                 # the encoder's format: converted on the device, half the bytes downloaded
+        from .egress import EgressYuv
+        egress = EgressYuv(dev, (h, w), layout=out_pix_fmt, matrix=out_matrix, range=out_range)
+    out_shape = (B, h, w, 3) if egress is None else (B, egress.frame_bytes)    # what is downloaded and handed to the writer
+    pin_out = [torch.empty(out_shape, dtype=torch.uint8).pin_memory() for _ in range(NS)]
     dev_in = [torch.empty((B, h, w, 3), dtype=torch.uint8, device=dev) for _ in range(NS)]
     dev_out = [torch.empty((B, h, w, 3), dtype=torch.uint8, device=dev) for _ in range(NS)]
+    dev_yuv = [torch.empty(out_shape, dtype=torch.uint8, device=dev) for _ in range(NS)] if egress is not None else None
     np_in = [t.numpy() for t in pin_in]
     np_out = [t.numpy() for t in pin_out]
     compute = torch.cuda.current_stream(dev)
@@ -215,6 +228,8 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                 if down_done[d] is not None:
                     compute.wait_event(down_done[d])
                 _, state = pipe.run(dev_in[d][:n], first_index=index, state=state, out=dev_out[d][:n])
+                if egress is not None:               # behind the chain on the compute stream; dev_yuv[d]'s last download was awaited above
+                    egress.run(dev_out[d][:n], out=dev_yuv[d][:n])
                 kd = torch.cuda.Event()
                 kd.record(compute)
                 kernels_done[d] = kd
@@ -223,7 +238,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                 # pin_out[d] was drained one iteration ago (drain below runs before the next batch is enqueued into the same slot)
                 s_down.wait_event(kd)
                 with torch.cuda.stream(s_down):
-                    pin_out[d][:n].copy_(dev_out[d][:n], non_blocking=True)
+                    pin_out[d][:n].copy_((dev_out if egress is None else dev_yuv)[d][:n], non_blocking=True)
                     dn = torch.cuda.Event()
                     dn.record(s_down)
                 down_done[d] = dn

@@ -282,3 +282,30 @@ def pil_resample_axis(n_in: int, n_out: int):
 
 def ptr(a) -> int:
     return 0 if a is None else a.ctypes.data
+
+
+_YUV_KR_KB = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
+
+
+def yuv_matrix(matrix: str = "bt601", rng: str = "tv"):
+    """The integer RGB -> Y'CbCr matrix of the egress stage (include/crtfx_egress.h) as (m int32[9], off int32[3]): rows Y, U, V in 16.16
+    fixed point, `off` = (16 or 0, 128, 128).  Every entry is floor(c * 65536 + 0.5) of the float64 BT.601 / BT.709 expression — limited
+    range ("tv") scales Y by 219/255 and the chroma rows by 224/255, full range ("pc") by 1 — and the G entry of each row is then set so that
+    the Y row sums to floor(sy * 65536 + 0.5) (white lands on 235 / 255 exactly) and both chroma rows sum to 0 (every grey gives U = V = 128)."""
+    if matrix not in _YUV_KR_KB:
+        raise ValueError(f"matrix must be one of {sorted(_YUV_KR_KB)}, got {matrix!r}")
+    if rng not in ("tv", "pc"):
+        raise ValueError(f"range must be 'tv' or 'pc', got {rng!r}")
+    kr, kb = (np.float64(v) for v in _YUV_KR_KB[matrix])
+    kg = np.float64(1.0) - kr - kb
+    sy, sc = (np.float64(219.0) / 255.0, np.float64(224.0) / 255.0) if rng == "tv" else (np.float64(1.0), np.float64(1.0))
+    cu, cv = np.float64(2.0) * (1.0 - kb), np.float64(2.0) * (1.0 - kr)
+    f = np.array([[kr * sy, kg * sy, kb * sy],
+                  [-kr / cu * sc, -kg / cu * sc, 0.5 * sc],
+                  [0.5 * sc, -kg / cv * sc, -kb / cv * sc]], dtype=np.float64)
+    m = np.floor(f * 65536.0 + 0.5).astype(np.int64)
+    m[0, 1] = int(np.floor(sy * 65536.0 + 0.5)) - m[0, 0] - m[0, 2]
+    m[1, 1] = -(m[1, 0] + m[1, 2])
+    m[2, 1] = -(m[2, 0] + m[2, 2])
+    off = np.array([16 if rng == "tv" else 0, 128, 128], dtype=np.int32)
+    return np.ascontiguousarray(m.reshape(9).astype(np.int32)), off
