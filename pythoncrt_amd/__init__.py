@@ -4,6 +4,7 @@
     from pythoncrt_amd import process_frames      # the loop of process_video (ref:1037-1131) over the caller's frame iterator and writer
     from pythoncrt_amd import IngestResize        # its first step (ref:1039-1041) on the device: Pillow's BILINEAR resize of uint8 frames
     from pythoncrt_amd import EgressYuv           # its last step (ref:970-1002, `-pix_fmt yuv420p`) on the device: rgb24 -> yuv420p / nv12
+    from pythoncrt_amd import UnpackYuv           # the step in front of it (the reader's `-pix_fmt rgb24`, ref:489-502) on the device: yuv420p / nv12 -> rgb24
 
 See DESIGN.md (path, kernels, roofline) and INTEGRATION.md (how the reference binds to it).
 """
@@ -11,7 +12,8 @@ from .effects import (DeviceState, TriadMask, VignetteMask, apply_crt_effect, ap
                       make_vignette)
 from .egress import EgressYuv
 from .ingest import IngestResize
-from .render import iter_rgb24, process_frames
+from .render import iter_rgb24, iter_yuv420, process_frames
+from .unpack import UnpackYuv
 
 __all__ = ["DeviceState", "TriadMask", "VignetteMask", "apply_crt_effect", "apply_static_effects", "make_triad_mask", "make_vignette",
-           "process_frames", "iter_rgb24", "IngestResize", "EgressYuv"]
+           "process_frames", "iter_rgb24", "iter_yuv420", "IngestResize", "EgressYuv", "UnpackYuv"]

@@ -19,6 +19,14 @@ pipe, and no conversion left for the encoder:
       python -m pythoncrt_amd.cli --input - --width 1920 --height 1080 --fps 30 --output - --out-pix-fmt yuv420p [effect flags] |
       ffmpeg -f rawvideo -pix_fmt yuv420p -s 1920x1080 -r 30 -i - out.mp4
 
+With `--in-pix-fmt yuv420p` (or `nv12`; `--in-matrix bt601|bt709`, `--in-range tv|pc`) the source frames are read in the decoder's 4:2:0
+format and converted to RGB on the GPU (include/crtfx_unpack.h): 1.5 bytes per pixel through the pipe, the pinned slot and PCIe instead of
+3, and no `-pix_fmt rgb24` conversion in front.  Both ends together — no host core touches a pixel:
+
+    ffmpeg -i in.mp4 -f rawvideo -pix_fmt nv12 - |
+      python -m pythoncrt_amd.cli --input - --width 1920 --height 1080 --fps 30 --output - --in-pix-fmt nv12 --out-pix-fmt nv12 [effect flags] |
+      ffmpeg -f rawvideo -pix_fmt nv12 -s 1920x1080 -r 30 -i - out.mp4
+
 `--gui`, `--gpu`, `--nvenc-preset`, `--encoder`, `--decoder`, `--crf` and `--bitrate` are accepted for
 compatibility and ignored (encode/decode/UI are not part of this path).  `--text*` rasterise the overlay on
 the host with Pillow (ref:366-414) and alpha-blend it on the GPU before or after the effects.
@@ -119,6 +127,19 @@ def add_output_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
                    help="format of the frames written: raw rgb24 (default), or planar yuv420p / semi-planar nv12 converted on the GPU (1.5 bytes per pixel)")
     p.add_argument("--out-matrix", type=str, default="bt601", choices=["bt601", "bt709"], help="yuv420p / nv12: the RGB -> Y'CbCr matrix")
     p.add_argument("--out-range", type=str, default="tv", choices=["tv", "pc"], help="yuv420p / nv12: limited (tv, 16-235) or full (pc) range")
+    return p
+
+
+IN_PIX_FMTS = ("rgb24", "yuv420p", "nv12")
+
+
+def add_input_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
+    """The input-format flags of `main` (not in the reference, whose reader pipe is always `-pix_fmt rgb24`, ref:489-502).  Kept out of
+    `build_parser`, as `add_output_flags` is."""
+    p.add_argument("--in-pix-fmt", type=str, default="rgb24", choices=list(IN_PIX_FMTS),
+                   help="format of the frames read: raw rgb24 (default), or planar yuv420p / semi-planar nv12 converted on the GPU (1.5 bytes per pixel)")
+    p.add_argument("--in-matrix", type=str, default="bt601", choices=["bt601", "bt709"], help="yuv420p / nv12 input: the Y'CbCr -> RGB matrix")
+    p.add_argument("--in-range", type=str, default="tv", choices=["tv", "pc"], help="yuv420p / nv12 input: limited (tv, 16-235) or full (pc) range")
     return p
 
 
@@ -831,6 +852,10 @@ def main_sharded(a, rank: int, world: int) -> int:
         # every rank writes its chunks at offsets of its own: those, and the downloads behind them, are rgb24-sized here
         raise SystemExit(f"--out-pix-fmt {a.out_pix_fmt} is not supported by the sharded CLI (one process per GPU writes rgb24 only); "
                          "run one process, or convert behind it")
+    if getattr(a, "in_pix_fmt", "rgb24") != "rgb24":
+        # every rank reads its chunks at offsets of its own: those, and the uploads behind them, are rgb24-sized here
+        raise SystemExit(f"--in-pix-fmt {a.in_pix_fmt} is not supported by the sharded CLI (one process per GPU reads rgb24 only); "
+                         "run one process, or convert in front of it")
     import os
     import torch
     import torch.distributed as dist
@@ -958,16 +983,16 @@ def main_sharded(a, rank: int, world: int) -> int:
 
 
 def main(argv=None) -> int:
-    a = add_output_flags(build_parser()).parse_args(argv)
+    a = add_input_flags(add_output_flags(build_parser())).parse_args(argv)
     import os as _os
     if int(_os.environ.get("WORLD_SIZE", "1")) > 1 or _os.environ.get("CRTFX_FORCE_DIST") == "1":
         if a.gui or not a.input or a.width <= 0 or a.height <= 0:
             raise SystemExit("pass --input, --width and --height")
         return main_sharded(a, int(_os.environ.get("RANK", "0")), int(_os.environ.get("WORLD_SIZE", "1")))
     if a.gui or not a.input:
-        raise SystemExit("the GUI is not part of this path; pass --input (raw rgb24 file or '-')")
+        raise SystemExit("the GUI is not part of this path; pass --input (raw rgb24 / yuv420p / nv12 file or '-')")
     if a.width <= 0 or a.height <= 0:
-        raise SystemExit("raw rgb24 input needs --width and --height")
+        raise SystemExit("raw input needs --width and --height")
     import os
     t_start = time.perf_counter()
     import torch
@@ -996,6 +1021,15 @@ def main(argv=None) -> int:
         egress = EgressYuv(dev, (h, w), layout=a.out_pix_fmt, matrix=a.out_matrix, range=a.out_range)
     out_bytes = frame_bytes if egress is None else egress.frame_bytes
     out_shape = (B, h, w, 3) if egress is None else (B, out_bytes)
+    # --in-pix-fmt yuv420p / nv12, the mirror image: the frames are converted to RGB on the device in front of the chain (UnpackYuv) and
+    # everything upstream — the reader's frame size, the input's length in frames, the pinned and device input slots, the upload — is in
+    # frames of in_bytes instead of frame_bytes
+    unpack = None
+    if a.in_pix_fmt != "rgb24":
+        from .unpack import UnpackYuv
+        unpack = UnpackYuv(dev, (h, w), layout=a.in_pix_fmt, matrix=a.in_matrix, range=a.in_range)
+    in_bytes = frame_bytes if unpack is None else unpack.frame_bytes
+    in_shape = (B, h, w, 3) if unpack is None else (B, in_bytes)
     t0 = time.perf_counter()
     # regular files: positional I/O on a few threads (a pipe / the terminal: the plain sequential calls)
     in_pos = _seekable(fin) and a.input != "-"
@@ -1015,7 +1049,7 @@ def main(argv=None) -> int:
     # up front (the zero-copy download); a stream's length is unknown, its output goes through the pinned slots
     out_plan = None
     if in_pos and out_pos:
-        n_total = os.fstat(fin.fileno()).st_size // frame_bytes
+        n_total = os.fstat(fin.fileno()).st_size // in_bytes
         out_plan = [(k * B * out_bytes, min(B, n_total - k * B) * out_bytes) for k in range((n_total + B - 1) // B)] or None
         if presize and out_pos:
             os.ftruncate(fout.fileno(), n_total * out_bytes)
@@ -1024,15 +1058,16 @@ def main(argv=None) -> int:
         off = 0
         while True:
             yield (off if in_pos else None), B
-            off += B * frame_bytes
+            off += B * in_bytes
     NS = 3
-    reader = _Reader(fin, in_pos, jobs(), (B, h, w, 3), frame_bytes, slots=NS, io=a.io, autostart=False)
+    reader = _Reader(fin, in_pos, jobs(), in_shape, in_bytes, slots=NS, io=a.io, autostart=False)
     writer = _Writer(fout, out_pos, out_shape, out_bytes, slots=NS, plan=out_plan, io=a.io)
     t_pipe = time.perf_counter()                                    # the pipeline proper: first read issued ... last batch written (the --staging-report line)
     t_slots = t_pipe - t_start - t_imports - t_engine
     reader.start()
     dev_in = [torch.empty((B, h, w, 3), dtype=torch.uint8, device=dev) for _ in range(NS)]
     dev_out = [torch.empty((B, h, w, 3), dtype=torch.uint8, device=dev) for _ in range(NS)]
+    dev_recv = dev_in if unpack is None else [torch.empty(in_shape, dtype=torch.uint8, device=dev) for _ in range(NS)]         # what is uploaded
     dev_send = dev_out if egress is None else [torch.empty(out_shape, dtype=torch.uint8, device=dev) for _ in range(NS)]      # what is downloaded
     compute = torch.cuda.current_stream(dev)
     s_up, s_down = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
@@ -1058,7 +1093,7 @@ def main(argv=None) -> int:
                 tim = a.staging_report
                 if tim:
                     u0 = torch.cuda.Event(enable_timing=True); u0.record(s_up)
-                reader.upload(i, n, dev_in[d], s_up)              # from the pinned slot, or straight from the registered file mapping
+                reader.upload(i, n, dev_recv[d], s_up)            # from the pinned slot, or straight from the registered file mapping
                 up = torch.cuda.Event(enable_timing=tim)
                 up.record(s_up)
                 # kernels k behind the upload, and behind the download that last read this output slot
@@ -1067,6 +1102,8 @@ def main(argv=None) -> int:
                     compute.wait_event(down_done[d])
                 if tim:
                     k0 = torch.cuda.Event(enable_timing=True); k0.record(compute)
+                if unpack is not None:                            # on the compute stream, behind the upload and behind the chain that last read
+                    unpack.run(dev_recv[d][:n], out=dev_in[d][:n])    # dev_in[d] (batch k - NS, same stream): counted with the kernels below
                 _, state = pipe.run(dev_in[d][:n], first_index=index, state=state, out=dev_out[d][:n])
                 if egress is not None:                            # on the compute stream, behind the chain: counted with the kernels below
                     egress.run(dev_out[d][:n], out=dev_send[d][:n])
@@ -1105,7 +1142,7 @@ def main(argv=None) -> int:
                 reader.release(i)
             index += n
             k += 1
-            if got < B * frame_bytes:
+            if got < B * in_bytes:
                 break
         if pend is not None:
             pend[0].synchronize()
@@ -1150,10 +1187,10 @@ def main(argv=None) -> int:
         k_ms = sum(m[2].elapsed_time(m[3]) for m in mk) / len(mk)
         dn_ms = sum(m[4].elapsed_time(m[5]) for m in mk) / len(mk)
         span = mk[0][0].elapsed_time(mk[-1][5]) / len(mk)
-        nb = sum(m[6] for m in mk) / len(mk) * frame_bytes
-        nb_out = nb / frame_bytes * out_bytes
-        print(f"staging (GPU side, per batch of {nb / frame_bytes:.0f} frames): upload {up_ms:.2f} ms = {nb / up_ms / 1e6:.1f} GB/s, kernels {k_ms:.2f} ms, "
-              f"download {dn_ms:.2f} ms = {nb_out / dn_ms / 1e6:.1f} GB/s; one batch every {span:.2f} ms = {nb / frame_bytes / span * 1e3:.0f} frames/s", file=sys.stderr)
+        nf = sum(m[6] for m in mk) / len(mk)
+        nb, nb_out = nf * in_bytes, nf * out_bytes
+        print(f"staging (GPU side, per batch of {nf:.0f} frames): upload {up_ms:.2f} ms = {nb / up_ms / 1e6:.1f} GB/s, kernels {k_ms:.2f} ms, "
+              f"download {dn_ms:.2f} ms = {nb_out / dn_ms / 1e6:.1f} GB/s; one batch every {span:.2f} ms = {nf / span * 1e3:.0f} frames/s", file=sys.stderr)
     if a.staging_report:
         # start-up (imports, ctx, tables, pinning the staging slots) and the exit are outside this figure; the reader's first read, the unoverlapped
         # legs of the first and last batch and the output's last write are inside it

@@ -44,6 +44,24 @@ def iter_rgb24(stream, out_w: int, out_h: int):
         yield np.frombuffer(buf, dtype=np.uint8).reshape((int(out_h), int(out_w), 3))
 
 
+def iter_yuv420(stream, w: int, h: int):
+    """`iter_rgb24` for an already open byte stream of raw yuv420p or nv12 (`-f rawvideo -pix_fmt yuv420p -` / `-pix_fmt nv12 -`): 1-D uint8
+    arrays of frame_bytes = h * w + 2 * ceil(h / 2) * ceil(w / 2) bytes — what `process_frames(..., in_pix_fmt=)` takes — until the stream
+    ends; the same short-read handling, a trailing partial frame is dropped.  Both layouts have the same size: the bytes are not interpreted here."""
+    from .egress import frame_bytes
+    frame_size = frame_bytes(int(h), int(w))
+    while True:
+        buf = stream.read(frame_size)
+        while buf and len(buf) < frame_size:           # a pipe may return less than asked for: keep reading until the frame is whole or the stream ends
+            more = stream.read(frame_size - len(buf))
+            if not more:
+                break
+            buf += more
+        if not buf or len(buf) < frame_size:
+            return
+        yield np.frombuffer(buf, dtype=np.uint8)
+
+
 def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.ndarray], None], out_w: int, out_h: int, fps_out: float,
                    total_frames: Optional[int] = None, *,
                    scanline_strength: float = 0.6, triad_strength: float = 0.35, triad_gamma: float = 2.2, triad_preserve_luma: bool = False,
@@ -56,7 +74,9 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                    text: str = "", text_font: str = "", text_size: int = 36, text_color: str = "#FFFFFF", text_pos: Tuple[int, int] = (32, 32),
                    text_after: bool = True, progress_cb: Optional[Callable[[float], None]] = None,
                    batch: int = 16, noise_seed: Optional[int] = None, device=None, resize_on: str = "device",
-                   out_pix_fmt: str = "rgb24", out_matrix: str = "bt601", out_range: str = "tv", **io_keywords) -> int:
+                   out_pix_fmt: str = "rgb24", out_matrix: str = "bt601", out_range: str = "tv",
+                   in_pix_fmt: str = "rgb24", in_matrix: str = "bt601", in_range: str = "tv", in_size: Optional[Tuple[int, int]] = None,
+                   **io_keywords) -> int:
     """Render every frame of `frame_iter` (H x W x 3 uint8 RGB arrays) and hand the finished uint8 frames to `write_frame` in order.
     Effect keywords: the names, meaning and defaults of process_video / the CLI (ref:864-911, :1155-1206); the caller applies the clamps of
     ref:1225-1266 as the reference's `main` does (`pythoncrt_amd.cli.settings_from_args` restates them).  Returns the number of frames written.
@@ -72,6 +92,12 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     `-pix_fmt yuv420p`, ref:970-1002): the finished frames are converted on the device behind the chain (EgressYuv, include/crtfx_egress.h:
     `out_matrix` "bt601" / "bt709", `out_range` "tv" / "pc"), only frame_bytes = h * w + 2 * ceil(h / 2) * ceil(w / 2) bytes per frame are
     downloaded, and `write_frame` receives a 1-D uint8 array of that many bytes.  "rgb24" (default) is the path as it was.
+    `in_pix_fmt="yuv420p"` / `"nv12"` takes the decoder's format instead of rgb24: every item of `frame_iter` is then a uint8 array of
+    frame_bytes(*in_size) elements (any shape; it is flattened — `iter_yuv420` yields them), `in_size = (src_h, src_w)` defaulting to the
+    output size; the frames are staged and uploaded as 1.5 bytes per pixel and converted to RGB on the device in front of the chain
+    (UnpackYuv, include/crtfx_unpack.h: `in_matrix` "bt601" / "bt709", `in_range` "tv" / "pc"); where `in_size` differs from the output
+    size that RGB is resized by IngestResize.  `resize_on="host"` is refused with it (there is no host RGB frame to hand to Pillow).
+    "rgb24" (default) is the path as it was.
     If `frame_iter` or `write_frame` raises, the GPU work already queued is drained (device synchronize) before the exception leaves this
     function, so that the staging buffers are not freed under a running copy."""
     import os
@@ -84,6 +110,10 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         raise ValueError(f"resize_on must be 'device' or 'host', got {resize_on!r}")
     if out_pix_fmt not in ("rgb24", "yuv420p", "nv12"):
         raise ValueError(f"out_pix_fmt must be 'rgb24', 'yuv420p' or 'nv12', got {out_pix_fmt!r}")
+    if in_pix_fmt not in ("rgb24", "yuv420p", "nv12"):
+        raise ValueError(f"in_pix_fmt must be 'rgb24', 'yuv420p' or 'nv12', got {in_pix_fmt!r}")
+    if in_pix_fmt != "rgb24" and resize_on == "host":
+        raise ValueError(f"resize_on='host' cannot be combined with in_pix_fmt={in_pix_fmt!r}: there is no host RGB frame to hand to Pillow")
     if not torch.cuda.is_available():
         raise RuntimeError("no ROCm device visible; pythoncrt_amd has no CPU fallback")
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -107,7 +137,9 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     total = max(1, int(total_frames)) if total_frames else None
 
     NS = 2
-    pin_in = [torch.empty((B, h, w, 3), dtype=torch.uint8).pin_memory() for _ in range(NS)]
+    # a 4:2:0 input is staged in slots of its own size (_YuvSource below): no rgb24-sized pinned slot is needed then
+    pin_in = [torch.empty((B, h, w, 3), dtype=torch.uint8).pin_memory() if in_pix_fmt == "rgb24" else torch.empty((0, h, w, 3), dtype=torch.uint8)
+              for _ in range(NS)]
     egress = None
     if out_pix_fmt != "rgb24":                                                 # the encoder's format: converted on the device, half the bytes downloaded
         from .egress import EgressYuv
@@ -142,19 +174,57 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
             self.up_done = [None] * NS           # the upload that last read pin[d]
             self.kernels_done = [None] * NS      # the resize that last read dev[d]
 
+        def convert(self, d, n):
+            self.plan.run(self.dev[d][:n], out=dev_in[d][:n])                          # ref:1039-1041
+
+    YUV = "yuv"                      # the key of the one 4:2:0 source (its size is fixed by in_size)
+    yuv_hw = (h, w) if in_size is None else (int(in_size[0]), int(in_size[1]))
+    yuv_bytes = yuv_hw[0] * yuv_hw[1] + 2 * ((yuv_hw[0] + 1) // 2) * ((yuv_hw[1] + 1) // 2)
+
+    class _YuvSource:
+        """Staging of a 4:2:0 input: pinned and device slots of frame_bytes(*in_size) bytes per frame, the plan that converts them to RGB —
+        into dev_in[d] itself, or, where in_size is not the output size, into RGB slots of that size which IngestResize brings to dev_in[d]."""
+        def __init__(self):
+            from .unpack import UnpackYuv
+            self.plan = UnpackYuv(dev, yuv_hw, layout=in_pix_fmt, matrix=in_matrix, range=in_range)
+            self.nbytes = self.plan.frame_bytes
+            assert self.nbytes == yuv_bytes
+            self.resize, self.rgb = None, None
+            if yuv_hw != (h, w):
+                from .ingest import IngestResize
+                self.resize = IngestResize(dev, yuv_hw, (h, w))
+                self.rgb = [torch.empty((B,) + yuv_hw + (3,), dtype=torch.uint8, device=dev) for _ in range(NS)]
+            self.pin = [torch.empty((B, self.nbytes), dtype=torch.uint8).pin_memory() for _ in range(NS)]
+            self.dev = [torch.empty((B, self.nbytes), dtype=torch.uint8, device=dev) for _ in range(NS)]
+            self.np = [t.numpy() for t in self.pin]
+            self.up_done = [None] * NS           # the upload that last read pin[d]
+            self.kernels_done = [None] * NS      # the conversion that last read dev[d] (and, on the same stream, the resize that read rgb[d])
+
+        def convert(self, d, n):
+            if self.resize is None:
+                self.plan.run(self.dev[d][:n], out=dev_in[d][:n])
+            else:
+                self.plan.run(self.dev[d][:n], out=self.rgb[d][:n])
+                self.resize.run(self.rgb[d][:n], out=dev_in[d][:n])
+
     def source(key):
         src = sources.pop(key, None)
         if src is None:
             if len(sources) >= MAX_SOURCES:      # rare: drop the least recently used size once its queued work is done
                 torch.cuda.synchronize(dev)
                 sources.pop(next(iter(sources)))
-            src = _Source(*key)
+            src = _YuvSource() if key == YUV else _Source(*key)
         sources[key] = src
         return src
 
     def fit(frame):
         """(array to stage, None) for a frame at the output size or resized on the host; (array, (src_h, src_w)) for one the device resizes."""
         a = np.asarray(frame)
+        if in_pix_fmt != "rgb24":
+            a = a.reshape(-1)
+            if a.size != yuv_bytes:
+                raise ValueError(f"a {in_pix_fmt} frame of {yuv_hw[0]} x {yuv_hw[1]} holds {yuv_bytes} bytes, got an item of {a.size}")
+            return a, YUV
         if a.ndim != 3 or a.shape[2] != 3:
             raise ValueError(f"frames must be H x W x 3 RGB arrays, got {a.shape}")
         if a.shape[0] != h or a.shape[1] != w:                                  # ref:1039-1041
@@ -224,7 +294,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                     src.up_done[d] = up
                     compute.wait_event(up)
                     # dev_in[d]: its last upload (two batches ago) was awaited by `compute` then, its last readers ran on `compute`
-                    src.plan.run(src.dev[d][:n], out=dev_in[d][:n])                  # ref:1039-1041, on the compute stream
+                    src.convert(d, n)                                                # on the compute stream
                 if down_done[d] is not None:
                     compute.wait_event(down_done[d])
                 _, state = pipe.run(dev_in[d][:n], first_index=index, state=state, out=dev_out[d][:n])

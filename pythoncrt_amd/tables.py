@@ -309,3 +309,23 @@ def yuv_matrix(matrix: str = "bt601", rng: str = "tv"):
     m[2, 1] = -(m[2, 0] + m[2, 2])
     off = np.array([16 if rng == "tv" else 0, 128, 128], dtype=np.int32)
     return np.ascontiguousarray(m.reshape(9).astype(np.int32)), off
+
+
+def rgb_matrix(matrix: str = "bt601", rng: str = "tv"):
+    """The integer Y'CbCr -> RGB matrix of the source stage (include/crtfx_unpack.h) as (m int32[9], off int32[3]): rows R, G, B over the
+    columns (Y, U, V) in 16.16 fixed point, `off` = (16 or 0, 128, 128).  Every entry is floor(c * 65536 + 0.5) of the float64 BT.601 / BT.709
+    expression — limited range ("tv") scales the Y column by 255/219 and the chroma columns by 255/224, full range ("pc") by 1 — and none is
+    adjusted afterwards: the three Y entries are one number (every grey gives R = G = B), the R/U and B/V entries are exactly 0."""
+    if matrix not in _YUV_KR_KB:
+        raise ValueError(f"matrix must be one of {sorted(_YUV_KR_KB)}, got {matrix!r}")
+    if rng not in ("tv", "pc"):
+        raise ValueError(f"range must be 'tv' or 'pc', got {rng!r}")
+    kr, kb = (np.float64(v) for v in _YUV_KR_KB[matrix])
+    kg = np.float64(1.0) - kr - kb
+    sy, sc = (np.float64(255.0) / 219.0, np.float64(255.0) / 224.0) if rng == "tv" else (np.float64(1.0), np.float64(1.0))
+    f = np.array([[sy, 0.0, 2.0 * (1.0 - kr) * sc],
+                  [sy, -2.0 * kb * (1.0 - kb) / kg * sc, -2.0 * kr * (1.0 - kr) / kg * sc],
+                  [sy, 2.0 * (1.0 - kb) * sc, 0.0]], dtype=np.float64)
+    m = np.floor(f * 65536.0 + 0.5).astype(np.int64)
+    off = np.array([16 if rng == "tv" else 0, 128, 128], dtype=np.int32)
+    return np.ascontiguousarray(m.reshape(9).astype(np.int32)), off
