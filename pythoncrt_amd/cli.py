@@ -27,6 +27,13 @@ format and converted to RGB on the GPU (include/crtfx_unpack.h): 1.5 bytes per p
       python -m pythoncrt_amd.cli --input - --width 1920 --height 1080 --fps 30 --output - --in-pix-fmt nv12 --out-pix-fmt nv12 [effect flags] |
       ffmpeg -f rawvideo -pix_fmt nv12 -s 1920x1080 -r 30 -i - out.mp4
 
+With `yuv420p10le` or `p010le` on BOTH ends a 10-bit stream goes decoder -> chain -> encoder at 3 bytes per pixel each way and the chain runs
+on half pixels (include/crtfx_deep.h); one end only is refused:
+
+    ffmpeg -i in10.mkv -f rawvideo -pix_fmt p010le - |
+      python -m pythoncrt_amd.cli --input - --width 3840 --height 2160 --fps 30 --output - --in-pix-fmt p010le --out-pix-fmt yuv420p10le [effect flags] |
+      ffmpeg -f rawvideo -pix_fmt yuv420p10le -s 3840x2160 -r 30 -i - out.mkv
+
 `--gui`, `--gpu`, `--nvenc-preset`, `--encoder`, `--decoder`, `--crf` and `--bitrate` are accepted for
 compatibility and ignored (encode/decode/UI are not part of this path).  `--text*` rasterise the overlay on
 the host with Pillow (ref:366-414) and alpha-blend it on the GPU before or after the effects.
@@ -117,27 +124,30 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
-OUT_PIX_FMTS = ("rgb24", "yuv420p", "nv12")
+DEEP_PIX_FMTS = ("yuv420p10le", "p010le")     # 10-bit 4:2:0: on both ends or on neither (the chain then runs on half pixels)
+OUT_PIX_FMTS = ("rgb24", "yuv420p", "nv12") + DEEP_PIX_FMTS
 
 
 def add_output_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     """The output-format flags of `main` (not in the reference, whose encoder pipe is always rgb24 in and `-pix_fmt yuv420p` out, ref:970-1002).
     Kept out of `build_parser`, which restates the reference's schema plus the four additions listed there."""
     p.add_argument("--out-pix-fmt", type=str, default="rgb24", choices=list(OUT_PIX_FMTS),
-                   help="format of the frames written: raw rgb24 (default), or planar yuv420p / semi-planar nv12 converted on the GPU (1.5 bytes per pixel)")
+                   help="format of the frames written: raw rgb24 (default), or planar yuv420p / semi-planar nv12 converted on the GPU (1.5 bytes per pixel); "
+                        "yuv420p10le / p010le (3 bytes per pixel) with a 10-bit --in-pix-fmt: the chain then runs on half pixels")
     p.add_argument("--out-matrix", type=str, default="bt601", choices=["bt601", "bt709"], help="yuv420p / nv12: the RGB -> Y'CbCr matrix")
     p.add_argument("--out-range", type=str, default="tv", choices=["tv", "pc"], help="yuv420p / nv12: limited (tv, 16-235) or full (pc) range")
     return p
 
 
-IN_PIX_FMTS = ("rgb24", "yuv420p", "nv12")
+IN_PIX_FMTS = ("rgb24", "yuv420p", "nv12") + DEEP_PIX_FMTS
 
 
 def add_input_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     """The input-format flags of `main` (not in the reference, whose reader pipe is always `-pix_fmt rgb24`, ref:489-502).  Kept out of
     `build_parser`, as `add_output_flags` is."""
     p.add_argument("--in-pix-fmt", type=str, default="rgb24", choices=list(IN_PIX_FMTS),
-                   help="format of the frames read: raw rgb24 (default), or planar yuv420p / semi-planar nv12 converted on the GPU (1.5 bytes per pixel)")
+                   help="format of the frames read: raw rgb24 (default), or planar yuv420p / semi-planar nv12 converted on the GPU (1.5 bytes per pixel); "
+                        "yuv420p10le / p010le (3 bytes per pixel) with a 10-bit --out-pix-fmt: the chain then runs on half pixels")
     p.add_argument("--in-matrix", type=str, default="bt601", choices=["bt601", "bt709"], help="yuv420p / nv12 input: the Y'CbCr -> RGB matrix")
     p.add_argument("--in-range", type=str, default="tv", choices=["tv", "pc"], help="yuv420p / nv12 input: limited (tv, 16-235) or full (pc) range")
     return p
@@ -990,9 +1000,13 @@ def main(argv=None) -> int:
             raise SystemExit("pass --input, --width and --height")
         return main_sharded(a, int(_os.environ.get("RANK", "0")), int(_os.environ.get("WORLD_SIZE", "1")))
     if a.gui or not a.input:
-        raise SystemExit("the GUI is not part of this path; pass --input (raw rgb24 / yuv420p / nv12 file or '-')")
+        raise SystemExit("the GUI is not part of this path; pass --input (raw rgb24 / yuv420p / nv12 / yuv420p10le / p010le file or '-')")
     if a.width <= 0 or a.height <= 0:
         raise SystemExit("raw input needs --width and --height")
+    deep = a.in_pix_fmt in DEEP_PIX_FMTS
+    if deep != (a.out_pix_fmt in DEEP_PIX_FMTS):
+        raise SystemExit(f"--in-pix-fmt {a.in_pix_fmt} with --out-pix-fmt {a.out_pix_fmt}: a 10-bit format on one end only; the chain between them "
+                         "runs on half pixels or on uint8 ones — pass yuv420p10le / p010le on both ends or on neither")
     import os
     t_start = time.perf_counter()
     import torch
@@ -1007,7 +1021,8 @@ def main(argv=None) -> int:
     dev = torch.device("cuda", torch.cuda.current_device())
     seed = a.noise_seed if a.noise_seed is not None else int.from_bytes(os.urandom(8), "little")
     overlay = make_text_overlay_rgba(w, h, a.text, a.text_font, a.text_size, a.text_color, (a.text_x, a.text_y)) if a.text else None   # ref:1076
-    pipe = FramePipeline(dev, h, w, rs, fps=fps_out, noise_seed=seed, text_overlay_rgba=overlay, text_overlay_after=bool(a.text_after))
+    pix = torch.float16 if deep else torch.uint8                   # 10-bit 4:2:0 on both ends: the chain runs on half pixels (include/crtfx_deep.h)
+    pipe = FramePipeline(dev, h, w, rs, fps=fps_out, noise_seed=seed, dtype=pix, text_overlay_rgba=overlay, text_overlay_after=bool(a.text_after))
     t_engine = time.perf_counter() - t_start - t_imports
     fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb", buffering=0)
     out_path = a.output if a.output else (a.input + "_crt.rgb" if a.input != "-" else "-")
@@ -1017,7 +1032,10 @@ def main(argv=None) -> int:
     # and pinned output slots, the download, the output file's offsets and size — is in frames of out_bytes instead of frame_bytes
     egress = None
     if a.out_pix_fmt != "rgb24":
-        from .egress import EgressYuv
+        if deep:
+            from .deep import EgressYuv10 as EgressYuv
+        else:
+            from .egress import EgressYuv
         egress = EgressYuv(dev, (h, w), layout=a.out_pix_fmt, matrix=a.out_matrix, range=a.out_range)
     out_bytes = frame_bytes if egress is None else egress.frame_bytes
     out_shape = (B, h, w, 3) if egress is None else (B, out_bytes)
@@ -1026,7 +1044,10 @@ def main(argv=None) -> int:
     # frames of in_bytes instead of frame_bytes
     unpack = None
     if a.in_pix_fmt != "rgb24":
-        from .unpack import UnpackYuv
+        if deep:
+            from .deep import UnpackYuv10 as UnpackYuv
+        else:
+            from .unpack import UnpackYuv
         unpack = UnpackYuv(dev, (h, w), layout=a.in_pix_fmt, matrix=a.in_matrix, range=a.in_range)
     in_bytes = frame_bytes if unpack is None else unpack.frame_bytes
     in_shape = (B, h, w, 3) if unpack is None else (B, in_bytes)
@@ -1065,8 +1086,8 @@ def main(argv=None) -> int:
     t_pipe = time.perf_counter()                                    # the pipeline proper: first read issued ... last batch written (the --staging-report line)
     t_slots = t_pipe - t_start - t_imports - t_engine
     reader.start()
-    dev_in = [torch.empty((B, h, w, 3), dtype=torch.uint8, device=dev) for _ in range(NS)]
-    dev_out = [torch.empty((B, h, w, 3), dtype=torch.uint8, device=dev) for _ in range(NS)]
+    dev_in = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]
+    dev_out = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]
     dev_recv = dev_in if unpack is None else [torch.empty(in_shape, dtype=torch.uint8, device=dev) for _ in range(NS)]         # what is uploaded
     dev_send = dev_out if egress is None else [torch.empty(out_shape, dtype=torch.uint8, device=dev) for _ in range(NS)]      # what is downloaded
     compute = torch.cuda.current_stream(dev)

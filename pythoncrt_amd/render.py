@@ -22,6 +22,7 @@ import numpy as np
 
 # process_video keywords that belong to its container / codec plumbing (out of scope): accepted so that a caller can forward its
 # own keyword dictionary unchanged, and ignored
+_DEEP_FMTS = ("yuv420p10le", "p010le")          # the 10-bit 4:2:0 formats: both ends or neither (process_frames)
 _IO_KEYS = ("input_path", "output_path", "width", "height", "fps", "crf", "target_bitrate_kbps", "gpu", "nvenc_preset", "encoder_preference",
             "decoder_preference")
 
@@ -44,12 +45,16 @@ def iter_rgb24(stream, out_w: int, out_h: int):
         yield np.frombuffer(buf, dtype=np.uint8).reshape((int(out_h), int(out_w), 3))
 
 
-def iter_yuv420(stream, w: int, h: int):
+def iter_yuv420(stream, w: int, h: int, bits: int = 8):
     """`iter_rgb24` for an already open byte stream of raw yuv420p or nv12 (`-f rawvideo -pix_fmt yuv420p -` / `-pix_fmt nv12 -`): 1-D uint8
     arrays of frame_bytes = h * w + 2 * ceil(h / 2) * ceil(w / 2) bytes — what `process_frames(..., in_pix_fmt=)` takes — until the stream
-    ends; the same short-read handling, a trailing partial frame is dropped.  Both layouts have the same size: the bytes are not interpreted here."""
+    ends; the same short-read handling, a trailing partial frame is dropped.  Both layouts have the same size: the bytes are not interpreted here.
+    `bits=10` reads yuv420p10le / p010le (`-pix_fmt yuv420p10le -` / `-pix_fmt p010le -`): the same, with frames of twice as many bytes
+    (16-bit little-endian words), still handed out as 1-D uint8 arrays."""
     from .egress import frame_bytes
-    frame_size = frame_bytes(int(h), int(w))
+    if bits not in (8, 10):
+        raise ValueError(f"bits must be 8 or 10, got {bits!r}")
+    frame_size = frame_bytes(int(h), int(w)) * (2 if bits == 10 else 1)
     while True:
         buf = stream.read(frame_size)
         while buf and len(buf) < frame_size:           # a pipe may return less than asked for: keep reading until the frame is whole or the stream ends
@@ -98,6 +103,12 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     (UnpackYuv, include/crtfx_unpack.h: `in_matrix` "bt601" / "bt709", `in_range` "tv" / "pc"); where `in_size` differs from the output
     size that RGB is resized by IngestResize.  `resize_on="host"` is refused with it (there is no host RGB frame to hand to Pillow).
     "rgb24" (default) is the path as it was.
+    `in_pix_fmt` and `out_pix_fmt` both "yuv420p10le" / "p010le" (either layout on either end) is the 10-bit path: the chain runs on half
+    pixels (FramePipeline(dtype=torch.float16)), UnpackYuv10 stands in front of it and EgressYuv10 behind it (include/crtfx_deep.h, same
+    matrix and range keywords), items of `frame_iter` and the arrays handed to `write_frame` are 1-D uint8 arrays of
+    2 * (h * w + 2 * ceil(h / 2) * ceil(w / 2)) bytes (`iter_yuv420(..., bits=10)` yields them; 16-bit arrays of half as many words are
+    taken too).  Refused with ValueError before a device is touched: a 10-bit format on one end only (the 8-bit stages have no half path,
+    the 10-bit ones no uint8 path), `in_size` other than the output size (IngestResize has no half path), `resize_on="host"`.
     If `frame_iter` or `write_frame` raises, the GPU work already queued is drained (device synchronize) before the exception leaves this
     function, so that the staging buffers are not freed under a running copy."""
     import os
@@ -108,10 +119,17 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         raise TypeError(f"process_frames() got unexpected keyword arguments {sorted(unknown)}")
     if resize_on not in ("device", "host"):
         raise ValueError(f"resize_on must be 'device' or 'host', got {resize_on!r}")
-    if out_pix_fmt not in ("rgb24", "yuv420p", "nv12"):
-        raise ValueError(f"out_pix_fmt must be 'rgb24', 'yuv420p' or 'nv12', got {out_pix_fmt!r}")
-    if in_pix_fmt not in ("rgb24", "yuv420p", "nv12"):
-        raise ValueError(f"in_pix_fmt must be 'rgb24', 'yuv420p' or 'nv12', got {in_pix_fmt!r}")
+    if out_pix_fmt not in ("rgb24", "yuv420p", "nv12") + _DEEP_FMTS:
+        raise ValueError(f"out_pix_fmt must be 'rgb24', 'yuv420p' or 'nv12' (or, with a 10-bit input, 'yuv420p10le' or 'p010le'), got {out_pix_fmt!r}")
+    if in_pix_fmt not in ("rgb24", "yuv420p", "nv12") + _DEEP_FMTS:
+        raise ValueError(f"in_pix_fmt must be 'rgb24', 'yuv420p' or 'nv12' (or, with a 10-bit output, 'yuv420p10le' or 'p010le'), got {in_pix_fmt!r}")
+    deep = in_pix_fmt in _DEEP_FMTS
+    if deep != (out_pix_fmt in _DEEP_FMTS):
+        raise ValueError(f"in_pix_fmt={in_pix_fmt!r} with out_pix_fmt={out_pix_fmt!r}: a 10-bit format on one end only — the chain between "
+                         "them runs on half pixels or on uint8 ones, and the 8-bit stages have no half path (the 10-bit ones no uint8 path)")
+    if deep and in_size is not None and (int(in_size[0]), int(in_size[1])) != (int(out_h), int(out_w)):
+        raise ValueError(f"in_size={tuple(in_size)} differs from the output size {(int(out_h), int(out_w))}: a 10-bit input cannot be "
+                         "resized (IngestResize has no half path)")
     if in_pix_fmt != "rgb24" and resize_on == "host":
         raise ValueError(f"resize_on='host' cannot be combined with in_pix_fmt={in_pix_fmt!r}: there is no host RGB frame to hand to Pillow")
     if not torch.cuda.is_available():
@@ -133,7 +151,8 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         from .text import make_text_overlay_rgba
         overlay = make_text_overlay_rgba(w, h, text, text_font, int(text_size), text_color, tuple(text_pos))
     seed = int(noise_seed) if noise_seed is not None else int.from_bytes(os.urandom(8), "little")
-    pipe = FramePipeline(dev, h, w, rs, fps=float(fps_out), noise_seed=seed, text_overlay_rgba=overlay, text_overlay_after=bool(text_after))
+    pix = torch.float16 if deep else torch.uint8                               # what the chain runs on
+    pipe = FramePipeline(dev, h, w, rs, fps=float(fps_out), noise_seed=seed, dtype=pix, text_overlay_rgba=overlay, text_overlay_after=bool(text_after))
     total = max(1, int(total_frames)) if total_frames else None
 
     NS = 2
@@ -142,12 +161,15 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
               for _ in range(NS)]
     egress = None
     if out_pix_fmt != "rgb24":                                                 # the encoder's format: converted on the device, half the bytes downloaded
-        from .egress import EgressYuv
+        if deep:
+            from .deep import EgressYuv10 as EgressYuv
+        else:
+            from .egress import EgressYuv
         egress = EgressYuv(dev, (h, w), layout=out_pix_fmt, matrix=out_matrix, range=out_range)
     out_shape = (B, h, w, 3) if egress is None else (B, egress.frame_bytes)    # what is downloaded and handed to the writer
     pin_out = [torch.empty(out_shape, dtype=torch.uint8).pin_memory() for _ in range(NS)]
-    dev_in = [torch.empty((B, h, w, 3), dtype=torch.uint8, device=dev) for _ in range(NS)]
-    dev_out = [torch.empty((B, h, w, 3), dtype=torch.uint8, device=dev) for _ in range(NS)]
+    dev_in = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]
+    dev_out = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]
     dev_yuv = [torch.empty(out_shape, dtype=torch.uint8, device=dev) for _ in range(NS)] if egress is not None else None
     np_in = [t.numpy() for t in pin_in]
     np_out = [t.numpy() for t in pin_out]
@@ -179,13 +201,16 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
 
     YUV = "yuv"                      # the key of the one 4:2:0 source (its size is fixed by in_size)
     yuv_hw = (h, w) if in_size is None else (int(in_size[0]), int(in_size[1]))
-    yuv_bytes = yuv_hw[0] * yuv_hw[1] + 2 * ((yuv_hw[0] + 1) // 2) * ((yuv_hw[1] + 1) // 2)
+    yuv_bytes = (yuv_hw[0] * yuv_hw[1] + 2 * ((yuv_hw[0] + 1) // 2) * ((yuv_hw[1] + 1) // 2)) * (2 if deep else 1)
 
     class _YuvSource:
         """Staging of a 4:2:0 input: pinned and device slots of frame_bytes(*in_size) bytes per frame, the plan that converts them to RGB —
         into dev_in[d] itself, or, where in_size is not the output size, into RGB slots of that size which IngestResize brings to dev_in[d]."""
         def __init__(self):
-            from .unpack import UnpackYuv
+            if deep:
+                from .deep import UnpackYuv10 as UnpackYuv
+            else:
+                from .unpack import UnpackYuv
             self.plan = UnpackYuv(dev, yuv_hw, layout=in_pix_fmt, matrix=in_matrix, range=in_range)
             self.nbytes = self.plan.frame_bytes
             assert self.nbytes == yuv_bytes
@@ -222,6 +247,8 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         a = np.asarray(frame)
         if in_pix_fmt != "rgb24":
             a = a.reshape(-1)
+            if deep and a.dtype.itemsize == 2:       # 16-bit words: the same bytes
+                a = np.ascontiguousarray(a).view(np.uint8)
             if a.size != yuv_bytes:
                 raise ValueError(f"a {in_pix_fmt} frame of {yuv_hw[0]} x {yuv_hw[1]} holds {yuv_bytes} bytes, got an item of {a.size}")
             return a, YUV

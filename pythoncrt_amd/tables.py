@@ -329,3 +329,47 @@ def rgb_matrix(matrix: str = "bt601", rng: str = "tv"):
     m = np.floor(f * 65536.0 + 0.5).astype(np.int64)
     off = np.array([16 if rng == "tv" else 0, 128, 128], dtype=np.int32)
     return np.ascontiguousarray(m.reshape(9).astype(np.int32)), off
+
+
+def yuv_matrix10(matrix: str = "bt601", rng: str = "tv"):
+    """The integer RGB -> Y'CbCr matrix of the 10-bit egress stage (include/crtfx_deep.h) as (m int32[9], off int32[3]): `yuv_matrix`'s
+    recipe — floor(c * 65536 + 0.5) of the float64 expressions, then the G entry of each row set so that the Y row sums to
+    floor(sy * 65536 + 0.5) and both chroma rows sum to 0 — from quarter codes 0..1020 to 10-bit codes: sy = 876/1020 and sc = 896/1020
+    ("tv": exactly the 8-bit scales 219/255 and 224/255, so the matrix is yuv_matrix's) or both 1023/1020 ("pc"); `off` = (64 or 0, 512, 512)."""
+    if matrix not in _YUV_KR_KB:
+        raise ValueError(f"matrix must be one of {sorted(_YUV_KR_KB)}, got {matrix!r}")
+    if rng not in ("tv", "pc"):
+        raise ValueError(f"range must be 'tv' or 'pc', got {rng!r}")
+    kr, kb = (np.float64(v) for v in _YUV_KR_KB[matrix])
+    kg = np.float64(1.0) - kr - kb
+    sy, sc = (np.float64(876.0) / 1020.0, np.float64(896.0) / 1020.0) if rng == "tv" else (np.float64(1023.0) / 1020.0, np.float64(1023.0) / 1020.0)
+    cu, cv = np.float64(2.0) * (1.0 - kb), np.float64(2.0) * (1.0 - kr)
+    f = np.array([[kr * sy, kg * sy, kb * sy],
+                  [-kr / cu * sc, -kg / cu * sc, 0.5 * sc],
+                  [0.5 * sc, -kg / cv * sc, -kb / cv * sc]], dtype=np.float64)
+    m = np.floor(f * 65536.0 + 0.5).astype(np.int64)
+    m[0, 1] = int(np.floor(sy * 65536.0 + 0.5)) - m[0, 0] - m[0, 2]
+    m[1, 1] = -(m[1, 0] + m[1, 2])
+    m[2, 1] = -(m[2, 0] + m[2, 2])
+    off = np.array([64 if rng == "tv" else 0, 512, 512], dtype=np.int32)
+    return np.ascontiguousarray(m.reshape(9).astype(np.int32)), off
+
+
+def rgb_matrix10(matrix: str = "bt601", rng: str = "tv"):
+    """The integer Y'CbCr -> RGB matrix of the 10-bit source stage (include/crtfx_deep.h) as (m int32[9], off int32[3]): `rgb_matrix`'s
+    recipe — floor(c * 65536 + 0.5) of the float64 expressions, no entry adjusted — from 10-bit codes to quarter codes 0..1020:
+    sy' = 1020/876 and sc' = 1020/896 ("tv": exactly the 8-bit scales 255/219 and 255/224, so the matrix is rgb_matrix's) or both 1020/1023
+    ("pc"); `off` = (64 or 0, 512, 512)."""
+    if matrix not in _YUV_KR_KB:
+        raise ValueError(f"matrix must be one of {sorted(_YUV_KR_KB)}, got {matrix!r}")
+    if rng not in ("tv", "pc"):
+        raise ValueError(f"range must be 'tv' or 'pc', got {rng!r}")
+    kr, kb = (np.float64(v) for v in _YUV_KR_KB[matrix])
+    kg = np.float64(1.0) - kr - kb
+    sy, sc = (np.float64(1020.0) / 876.0, np.float64(1020.0) / 896.0) if rng == "tv" else (np.float64(1020.0) / 1023.0, np.float64(1020.0) / 1023.0)
+    f = np.array([[sy, 0.0, 2.0 * (1.0 - kr) * sc],
+                  [sy, -2.0 * kb * (1.0 - kb) / kg * sc, -2.0 * kr * (1.0 - kr) / kg * sc],
+                  [sy, 2.0 * (1.0 - kb) * sc, 0.0]], dtype=np.float64)
+    m = np.floor(f * 65536.0 + 0.5).astype(np.int64)
+    off = np.array([64 if rng == "tv" else 0, 512, 512], dtype=np.int32)
+    return np.ascontiguousarray(m.reshape(9).astype(np.int32)), off
