@@ -34,6 +34,13 @@ on half pixels (include/crtfx_deep.h); one end only is refused:
       python -m pythoncrt_amd.cli --input - --width 3840 --height 2160 --fps 30 --output - --in-pix-fmt p010le --out-pix-fmt yuv420p10le [effect flags] |
       ffmpeg -f rawvideo -pix_fmt yuv420p10le -s 3840x2160 -r 30 -i - out.mkv
 
+`yuv422p`, `yuyv422` and `uyvy422` (8-bit 4:2:2: capture cards, mezzanine codecs) are taken and written like the 8-bit 4:2:0 formats, on
+either end independently of the other (include/crtfx_422.h): 2 bytes per pixel, and the source's vertical chroma is kept on the way out:
+
+    ffmpeg -f v4l2 -i /dev/video0 -f rawvideo -pix_fmt uyvy422 - |
+      python -m pythoncrt_amd.cli --input - --width 1920 --height 1080 --fps 30 --output - --in-pix-fmt uyvy422 --out-pix-fmt yuv422p [effect flags] |
+      ffmpeg -f rawvideo -pix_fmt yuv422p -s 1920x1080 -r 30 -i - out.mov
+
 `--gui`, `--gpu`, `--nvenc-preset`, `--encoder`, `--decoder`, `--crf` and `--bitrate` are accepted for
 compatibility and ignored (encode/decode/UI are not part of this path).  `--text*` rasterise the overlay on
 the host with Pillow (ref:366-414) and alpha-blend it on the GPU before or after the effects.
@@ -125,7 +132,8 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 DEEP_PIX_FMTS = ("yuv420p10le", "p010le")     # 10-bit 4:2:0: on both ends or on neither (the chain then runs on half pixels)
-OUT_PIX_FMTS = ("rgb24", "yuv420p", "nv12") + DEEP_PIX_FMTS
+YUV422_PIX_FMTS = ("yuv422p", "yuyv422", "uyvy422")    # 8-bit 4:2:2: members of the 8-bit family, either end independently of the other
+OUT_PIX_FMTS = ("rgb24", "yuv420p", "nv12") + YUV422_PIX_FMTS + DEEP_PIX_FMTS
 
 
 def add_output_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
@@ -133,13 +141,14 @@ def add_output_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     Kept out of `build_parser`, which restates the reference's schema plus the four additions listed there."""
     p.add_argument("--out-pix-fmt", type=str, default="rgb24", choices=list(OUT_PIX_FMTS),
                    help="format of the frames written: raw rgb24 (default), or planar yuv420p / semi-planar nv12 converted on the GPU (1.5 bytes per pixel); "
+                        "planar yuv422p / packed yuyv422 / uyvy422 (2 bytes per pixel); "
                         "yuv420p10le / p010le (3 bytes per pixel) with a 10-bit --in-pix-fmt: the chain then runs on half pixels")
-    p.add_argument("--out-matrix", type=str, default="bt601", choices=["bt601", "bt709"], help="yuv420p / nv12: the RGB -> Y'CbCr matrix")
-    p.add_argument("--out-range", type=str, default="tv", choices=["tv", "pc"], help="yuv420p / nv12: limited (tv, 16-235) or full (pc) range")
+    p.add_argument("--out-matrix", type=str, default="bt601", choices=["bt601", "bt709"], help="yuv420p / nv12 / 4:2:2: the RGB -> Y'CbCr matrix")
+    p.add_argument("--out-range", type=str, default="tv", choices=["tv", "pc"], help="yuv420p / nv12 / 4:2:2: limited (tv, 16-235) or full (pc) range")
     return p
 
 
-IN_PIX_FMTS = ("rgb24", "yuv420p", "nv12") + DEEP_PIX_FMTS
+IN_PIX_FMTS = ("rgb24", "yuv420p", "nv12") + YUV422_PIX_FMTS + DEEP_PIX_FMTS
 
 
 def add_input_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
@@ -147,9 +156,10 @@ def add_input_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     `build_parser`, as `add_output_flags` is."""
     p.add_argument("--in-pix-fmt", type=str, default="rgb24", choices=list(IN_PIX_FMTS),
                    help="format of the frames read: raw rgb24 (default), or planar yuv420p / semi-planar nv12 converted on the GPU (1.5 bytes per pixel); "
+                        "planar yuv422p / packed yuyv422 / uyvy422 (2 bytes per pixel); "
                         "yuv420p10le / p010le (3 bytes per pixel) with a 10-bit --out-pix-fmt: the chain then runs on half pixels")
-    p.add_argument("--in-matrix", type=str, default="bt601", choices=["bt601", "bt709"], help="yuv420p / nv12 input: the Y'CbCr -> RGB matrix")
-    p.add_argument("--in-range", type=str, default="tv", choices=["tv", "pc"], help="yuv420p / nv12 input: limited (tv, 16-235) or full (pc) range")
+    p.add_argument("--in-matrix", type=str, default="bt601", choices=["bt601", "bt709"], help="yuv420p / nv12 / 4:2:2 input: the Y'CbCr -> RGB matrix")
+    p.add_argument("--in-range", type=str, default="tv", choices=["tv", "pc"], help="yuv420p / nv12 / 4:2:2 input: limited (tv, 16-235) or full (pc) range")
     return p
 
 
@@ -1000,7 +1010,7 @@ def main(argv=None) -> int:
             raise SystemExit("pass --input, --width and --height")
         return main_sharded(a, int(_os.environ.get("RANK", "0")), int(_os.environ.get("WORLD_SIZE", "1")))
     if a.gui or not a.input:
-        raise SystemExit("the GUI is not part of this path; pass --input (raw rgb24 / yuv420p / nv12 / yuv420p10le / p010le file or '-')")
+        raise SystemExit("the GUI is not part of this path; pass --input (raw rgb24 / yuv420p / nv12 / yuv422p / yuyv422 / uyvy422 / yuv420p10le / p010le file or '-')")
     if a.width <= 0 or a.height <= 0:
         raise SystemExit("raw input needs --width and --height")
     deep = a.in_pix_fmt in DEEP_PIX_FMTS
@@ -1028,24 +1038,28 @@ def main(argv=None) -> int:
     out_path = a.output if a.output else (a.input + "_crt.rgb" if a.input != "-" else "-")
     B = max(1, int(a.batch))
     frame_bytes = h * w * 3
-    # --out-pix-fmt yuv420p / nv12: the chain's frames are converted on the device behind it (EgressYuv) and everything downstream — the device
+    # --out-pix-fmt yuv420p / nv12 / yuv422p / yuyv422 / uyvy422: the chain's frames are converted on the device behind it (EgressYuv) and everything downstream — the device
     # and pinned output slots, the download, the output file's offsets and size — is in frames of out_bytes instead of frame_bytes
     egress = None
     if a.out_pix_fmt != "rgb24":
         if deep:
             from .deep import EgressYuv10 as EgressYuv
+        elif a.out_pix_fmt in YUV422_PIX_FMTS:
+            from .yuv422 import EgressYuv422 as EgressYuv
         else:
             from .egress import EgressYuv
         egress = EgressYuv(dev, (h, w), layout=a.out_pix_fmt, matrix=a.out_matrix, range=a.out_range)
     out_bytes = frame_bytes if egress is None else egress.frame_bytes
     out_shape = (B, h, w, 3) if egress is None else (B, out_bytes)
-    # --in-pix-fmt yuv420p / nv12, the mirror image: the frames are converted to RGB on the device in front of the chain (UnpackYuv) and
+    # --in-pix-fmt yuv420p / nv12 / yuv422p / yuyv422 / uyvy422, the mirror image: the frames are converted to RGB on the device in front of the chain (UnpackYuv) and
     # everything upstream — the reader's frame size, the input's length in frames, the pinned and device input slots, the upload — is in
     # frames of in_bytes instead of frame_bytes
     unpack = None
     if a.in_pix_fmt != "rgb24":
         if deep:
             from .deep import UnpackYuv10 as UnpackYuv
+        elif a.in_pix_fmt in YUV422_PIX_FMTS:
+            from .yuv422 import UnpackYuv422 as UnpackYuv
         else:
             from .unpack import UnpackYuv
         unpack = UnpackYuv(dev, (h, w), layout=a.in_pix_fmt, matrix=a.in_matrix, range=a.in_range)

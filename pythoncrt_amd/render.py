@@ -23,6 +23,7 @@ import numpy as np
 # process_video keywords that belong to its container / codec plumbing (out of scope): accepted so that a caller can forward its
 # own keyword dictionary unchanged, and ignored
 _DEEP_FMTS = ("yuv420p10le", "p010le")          # the 10-bit 4:2:0 formats: both ends or neither (process_frames)
+_422_FMTS = ("yuv422p", "yuyv422", "uyvy422")   # the 8-bit 4:2:2 formats: members of the 8-bit family, either end
 _IO_KEYS = ("input_path", "output_path", "width", "height", "fps", "crf", "target_bitrate_kbps", "gpu", "nvenc_preset", "encoder_preference",
             "decoder_preference")
 
@@ -55,6 +56,24 @@ def iter_yuv420(stream, w: int, h: int, bits: int = 8):
     if bits not in (8, 10):
         raise ValueError(f"bits must be 8 or 10, got {bits!r}")
     frame_size = frame_bytes(int(h), int(w)) * (2 if bits == 10 else 1)
+    while True:
+        buf = stream.read(frame_size)
+        while buf and len(buf) < frame_size:           # a pipe may return less than asked for: keep reading until the frame is whole or the stream ends
+            more = stream.read(frame_size - len(buf))
+            if not more:
+                break
+            buf += more
+        if not buf or len(buf) < frame_size:
+            return
+        yield np.frombuffer(buf, dtype=np.uint8)
+
+
+def iter_yuv422(stream, w: int, h: int, layout: str):
+    """`iter_yuv420` for an already open byte stream of raw yuv422p, yuyv422 or uyvy422 (`-f rawvideo -pix_fmt uyvy422 -`): 1-D uint8 arrays of
+    yuv422.frame_bytes(h, w, layout) bytes — what `process_frames(..., in_pix_fmt=layout)` takes — until the stream ends; the same
+    short-read handling, a trailing partial frame is dropped.  The bytes are not interpreted here."""
+    from .yuv422 import frame_bytes
+    frame_size = frame_bytes(int(h), int(w), layout)
     while True:
         buf = stream.read(frame_size)
         while buf and len(buf) < frame_size:           # a pipe may return less than asked for: keep reading until the frame is whole or the stream ends
@@ -103,6 +122,11 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     (UnpackYuv, include/crtfx_unpack.h: `in_matrix` "bt601" / "bt709", `in_range` "tv" / "pc"); where `in_size` differs from the output
     size that RGB is resized by IngestResize.  `resize_on="host"` is refused with it (there is no host RGB frame to hand to Pillow).
     "rgb24" (default) is the path as it was.
+    "yuv422p", "yuyv422" and "uyvy422" (8-bit 4:2:2, what capture cards and mezzanine codecs hand out) are members of the same 8-bit family
+    on either end, independently of the other end: UnpackYuv422 stands in front of the chain and EgressYuv422 behind it
+    (include/crtfx_422.h, the same matrix and range keywords), items of `frame_iter` (`iter_yuv422` yields them) and the arrays handed to
+    `write_frame` are 1-D uint8 arrays of yuv422.frame_bytes(h, w, layout) bytes — 2 per pixel — and an off-size 4:2:2 source goes through
+    IngestResize behind the source stage as a 4:2:0 one does.
     `in_pix_fmt` and `out_pix_fmt` both "yuv420p10le" / "p010le" (either layout on either end) is the 10-bit path: the chain runs on half
     pixels (FramePipeline(dtype=torch.float16)), UnpackYuv10 stands in front of it and EgressYuv10 behind it (include/crtfx_deep.h, same
     matrix and range keywords), items of `frame_iter` and the arrays handed to `write_frame` are 1-D uint8 arrays of
@@ -119,10 +143,12 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         raise TypeError(f"process_frames() got unexpected keyword arguments {sorted(unknown)}")
     if resize_on not in ("device", "host"):
         raise ValueError(f"resize_on must be 'device' or 'host', got {resize_on!r}")
-    if out_pix_fmt not in ("rgb24", "yuv420p", "nv12") + _DEEP_FMTS:
-        raise ValueError(f"out_pix_fmt must be 'rgb24', 'yuv420p' or 'nv12' (or, with a 10-bit input, 'yuv420p10le' or 'p010le'), got {out_pix_fmt!r}")
-    if in_pix_fmt not in ("rgb24", "yuv420p", "nv12") + _DEEP_FMTS:
-        raise ValueError(f"in_pix_fmt must be 'rgb24', 'yuv420p' or 'nv12' (or, with a 10-bit output, 'yuv420p10le' or 'p010le'), got {in_pix_fmt!r}")
+    if out_pix_fmt not in ("rgb24", "yuv420p", "nv12") + _422_FMTS + _DEEP_FMTS:
+        raise ValueError("out_pix_fmt must be 'rgb24', 'yuv420p' or 'nv12', 'yuv422p', 'yuyv422' or 'uyvy422' (or, with a 10-bit input, "
+                         f"'yuv420p10le' or 'p010le'), got {out_pix_fmt!r}")
+    if in_pix_fmt not in ("rgb24", "yuv420p", "nv12") + _422_FMTS + _DEEP_FMTS:
+        raise ValueError("in_pix_fmt must be 'rgb24', 'yuv420p' or 'nv12', 'yuv422p', 'yuyv422' or 'uyvy422' (or, with a 10-bit output, "
+                         f"'yuv420p10le' or 'p010le'), got {in_pix_fmt!r}")
     deep = in_pix_fmt in _DEEP_FMTS
     if deep != (out_pix_fmt in _DEEP_FMTS):
         raise ValueError(f"in_pix_fmt={in_pix_fmt!r} with out_pix_fmt={out_pix_fmt!r}: a 10-bit format on one end only — the chain between "
@@ -156,13 +182,15 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     total = max(1, int(total_frames)) if total_frames else None
 
     NS = 2
-    # a 4:2:0 input is staged in slots of its own size (_YuvSource below): no rgb24-sized pinned slot is needed then
+    # a 4:2:0 / 4:2:2 input is staged in slots of its own size (_YuvSource below): no rgb24-sized pinned slot is needed then
     pin_in = [torch.empty((B, h, w, 3), dtype=torch.uint8).pin_memory() if in_pix_fmt == "rgb24" else torch.empty((0, h, w, 3), dtype=torch.uint8)
               for _ in range(NS)]
     egress = None
     if out_pix_fmt != "rgb24":                                                 # the encoder's format: converted on the device, half the bytes downloaded
         if deep:
             from .deep import EgressYuv10 as EgressYuv
+        elif out_pix_fmt in _422_FMTS:
+            from .yuv422 import EgressYuv422 as EgressYuv
         else:
             from .egress import EgressYuv
         egress = EgressYuv(dev, (h, w), layout=out_pix_fmt, matrix=out_matrix, range=out_range)
@@ -199,16 +227,22 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         def convert(self, d, n):
             self.plan.run(self.dev[d][:n], out=dev_in[d][:n])                          # ref:1039-1041
 
-    YUV = "yuv"                      # the key of the one 4:2:0 source (its size is fixed by in_size)
+    YUV = "yuv"                      # the key of the one 4:2:0 / 4:2:2 source (its size is fixed by in_size)
     yuv_hw = (h, w) if in_size is None else (int(in_size[0]), int(in_size[1]))
-    yuv_bytes = (yuv_hw[0] * yuv_hw[1] + 2 * ((yuv_hw[0] + 1) // 2) * ((yuv_hw[1] + 1) // 2)) * (2 if deep else 1)
+    if in_pix_fmt in _422_FMTS:
+        from .yuv422 import frame_bytes as _bytes422
+        yuv_bytes = _bytes422(yuv_hw[0], yuv_hw[1], in_pix_fmt)
+    else:
+        yuv_bytes = (yuv_hw[0] * yuv_hw[1] + 2 * ((yuv_hw[0] + 1) // 2) * ((yuv_hw[1] + 1) // 2)) * (2 if deep else 1)
 
     class _YuvSource:
-        """Staging of a 4:2:0 input: pinned and device slots of frame_bytes(*in_size) bytes per frame, the plan that converts them to RGB —
+        """Staging of a 4:2:0 or 4:2:2 input: pinned and device slots of frame_bytes(*in_size) bytes per frame, the plan that converts them to RGB —
         into dev_in[d] itself, or, where in_size is not the output size, into RGB slots of that size which IngestResize brings to dev_in[d]."""
         def __init__(self):
             if deep:
                 from .deep import UnpackYuv10 as UnpackYuv
+            elif in_pix_fmt in _422_FMTS:
+                from .yuv422 import UnpackYuv422 as UnpackYuv
             else:
                 from .unpack import UnpackYuv
             self.plan = UnpackYuv(dev, yuv_hw, layout=in_pix_fmt, matrix=in_matrix, range=in_range)
