@@ -14,8 +14,8 @@ LIB_PATH = os.environ.get("CRTFX_LIB") or os.path.join(_HERE, "libcrtfx.so")   #
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = [os.path.join(CSRC, f) for f in ("crtfx.hip", "crtfx_rr.hip", "crtfx_kernels.hip.h", "crtfx_common.hip.h", "crtfx_blur.hip.h", "crtfx_point.hip.h",
                                                 "crtfx_phosphor.hip.h", "crtfx_phosphor_ct.hip.h", "crtfx_warp.hip.h", "crtfx_internal.h", "crtfx_ingest.hip",
-                                                "crtfx_egress.hip", "crtfx_unpack.hip", "crtfx_deep.hip", "crtfx_422.hip")] + \
-          [os.path.join(ROOT, "include", f) for f in ("crtfx.h", "crtfx_ingest.h", "crtfx_egress.h", "crtfx_unpack.h", "crtfx_deep.h", "crtfx_422.h")]
+                                                "crtfx_egress.hip", "crtfx_unpack.hip", "crtfx_deep.hip", "crtfx_422.hip", "crtfx_444.hip")] + \
+          [os.path.join(ROOT, "include", f) for f in ("crtfx.h", "crtfx_ingest.h", "crtfx_egress.h", "crtfx_unpack.h", "crtfx_deep.h", "crtfx_422.h", "crtfx_444.h")]
 RR_RADII = tuple(range(1, 31))      # one register-window build per radius up to 30 (crtfx_internal.h); larger radii: the split path
 
 OK, E_INVALID, E_HIP, E_UNSUPPORTED, E_NOMEM = 0, -1, -2, -3, -4
@@ -158,6 +158,22 @@ for _fam in ("unpack422", "egress422"):
         f"crtfx_{_fam}_last_plan": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t]),
     })
 
+# ... and every symbol include/crtfx_444.h declares (the 10-bit 4:4:4 source and egress stages: two handle families, pythoncrt_amd/deep444.py)
+DEEP444_PLANAR, DEEP444_X2RGB10LE = 0, 1
+UNPACK444_OPT_FORCE_GENERAL = 1
+EGRESS444_OPT_FORCE_GENERAL = 1
+DEEP444_SYMBOLS = {}
+for _fam in ("unpack444", "egress444"):
+    DEEP444_SYMBOLS.update({
+        f"crtfx_{_fam}_create": (ctypes.c_int, [ctypes.c_int] * 5 + [_vp, _vp, ctypes.POINTER(_vp)]),
+        f"crtfx_{_fam}_destroy": (ctypes.c_int, [_vp]),
+        f"crtfx_{_fam}_last_error": (ctypes.c_char_p, [_vp]),
+        f"crtfx_{_fam}_frame_bytes": (ctypes.c_size_t, [_vp]),
+        f"crtfx_{_fam}_run": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
+        f"crtfx_{_fam}_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
+        f"crtfx_{_fam}_last_plan": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t]),
+    })
+
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC"]
 
 
@@ -181,6 +197,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), out: str =
     jobs.append([hipcc, *HIPCC_FLAGS, *extra_flags, *inc, "-c", os.path.join(CSRC, "crtfx_unpack.hip"), "-o", os.path.join(objdir, "crtfx_unpack.o")])
     jobs.append([hipcc, *HIPCC_FLAGS, *extra_flags, *inc, "-c", os.path.join(CSRC, "crtfx_deep.hip"), "-o", os.path.join(objdir, "crtfx_deep.o")])
     jobs.append([hipcc, *HIPCC_FLAGS, *extra_flags, *inc, "-c", os.path.join(CSRC, "crtfx_422.hip"), "-o", os.path.join(objdir, "crtfx_422.o")])
+    jobs.append([hipcc, *HIPCC_FLAGS, *extra_flags, *inc, "-c", os.path.join(CSRC, "crtfx_444.hip"), "-o", os.path.join(objdir, "crtfx_444.o")])
 
     def run(cmd):
         if verbose:
@@ -218,7 +235,7 @@ def build_variant(name: str, extra_flags, radii=(9,), main_tu: bool = False) -> 
     out = os.path.join(ROOT, "build", "ab", f"libcrtfx_{name}.so")
     subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out, main, *objs, os.path.join(base, "crtfx_ingest.o"),
                     os.path.join(base, "crtfx_egress.o"), os.path.join(base, "crtfx_unpack.o"), os.path.join(base, "crtfx_deep.o"),
-                    os.path.join(base, "crtfx_422.o")], check=True)
+                    os.path.join(base, "crtfx_422.o"), os.path.join(base, "crtfx_444.o")], check=True)
     return out
 
 
@@ -241,7 +258,7 @@ def load() -> ctypes.CDLL:
             "`python -c 'import __graft_entry__ as g; g.build()'` (or pythoncrt_amd._lib.build()). "
             "pythoncrt_amd has no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in {**SYMBOLS, **INGEST_SYMBOLS, **EGRESS_SYMBOLS, **UNPACK_SYMBOLS, **DEEP_SYMBOLS, **YUV422_SYMBOLS}.items():
+    for name, (res, args) in {**SYMBOLS, **INGEST_SYMBOLS, **EGRESS_SYMBOLS, **UNPACK_SYMBOLS, **DEEP_SYMBOLS, **YUV422_SYMBOLS, **DEEP444_SYMBOLS}.items():
         fn = getattr(lib, name)   # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

@@ -34,6 +34,15 @@ on half pixels (include/crtfx_deep.h); one end only is refused:
       python -m pythoncrt_amd.cli --input - --width 3840 --height 2160 --fps 30 --output - --in-pix-fmt p010le --out-pix-fmt yuv420p10le [effect flags] |
       ffmpeg -f rawvideo -pix_fmt yuv420p10le -s 3840x2160 -r 30 -i - out.mkv
 
+`yuv444p10le`, `gbrp10le` and `x2rgb10le` (10-bit 4:4:4: ProRes 4444 / DNxHR 444 decodes, DPX / TIFF / EXR sequences, screen capture) are
+members of that 10-bit family, in any pairing with it (include/crtfx_444.h): 6 bytes per pixel, 4 for x2rgb10le, no chroma sample dropped
+on either end; `--in-matrix` / `--in-range` / `--out-matrix` / `--out-range` apply to yuv444p10le, the two RGB formats are full range and
+ignore them:
+
+    ffmpeg -i prores4444.mov -f rawvideo -pix_fmt yuv444p10le - |
+      python -m pythoncrt_amd.cli --input - --width 1920 --height 1080 --fps 24 --output - --in-pix-fmt yuv444p10le --out-pix-fmt gbrp10le [effect flags] |
+      ffmpeg -f rawvideo -pix_fmt gbrp10le -s 1920x1080 -r 24 -i - out_%06d.dpx
+
 `yuv422p`, `yuyv422` and `uyvy422` (8-bit 4:2:2: capture cards, mezzanine codecs) are taken and written like the 8-bit 4:2:0 formats, on
 either end independently of the other (include/crtfx_422.h): 2 bytes per pixel, and the source's vertical chroma is kept on the way out:
 
@@ -132,8 +141,9 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 DEEP_PIX_FMTS = ("yuv420p10le", "p010le")     # 10-bit 4:2:0: on both ends or on neither (the chain then runs on half pixels)
+DEEP444_PIX_FMTS = ("yuv444p10le", "gbrp10le", "x2rgb10le")    # 10-bit 4:4:4: members of the 10-bit family, in any pairing with it
 YUV422_PIX_FMTS = ("yuv422p", "yuyv422", "uyvy422")    # 8-bit 4:2:2: members of the 8-bit family, either end independently of the other
-OUT_PIX_FMTS = ("rgb24", "yuv420p", "nv12") + YUV422_PIX_FMTS + DEEP_PIX_FMTS
+OUT_PIX_FMTS = ("rgb24", "yuv420p", "nv12") + YUV422_PIX_FMTS + DEEP_PIX_FMTS + DEEP444_PIX_FMTS
 
 
 def add_output_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
@@ -142,13 +152,14 @@ def add_output_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--out-pix-fmt", type=str, default="rgb24", choices=list(OUT_PIX_FMTS),
                    help="format of the frames written: raw rgb24 (default), or planar yuv420p / semi-planar nv12 converted on the GPU (1.5 bytes per pixel); "
                         "planar yuv422p / packed yuyv422 / uyvy422 (2 bytes per pixel); "
-                        "yuv420p10le / p010le (3 bytes per pixel) with a 10-bit --in-pix-fmt: the chain then runs on half pixels")
+                        "yuv420p10le / p010le (3 bytes per pixel) or yuv444p10le / gbrp10le (6) / x2rgb10le (4) with a 10-bit --in-pix-fmt: the chain "
+                        "then runs on half pixels")
     p.add_argument("--out-matrix", type=str, default="bt601", choices=["bt601", "bt709"], help="yuv420p / nv12 / 4:2:2: the RGB -> Y'CbCr matrix")
     p.add_argument("--out-range", type=str, default="tv", choices=["tv", "pc"], help="yuv420p / nv12 / 4:2:2: limited (tv, 16-235) or full (pc) range")
     return p
 
 
-IN_PIX_FMTS = ("rgb24", "yuv420p", "nv12") + YUV422_PIX_FMTS + DEEP_PIX_FMTS
+IN_PIX_FMTS = ("rgb24", "yuv420p", "nv12") + YUV422_PIX_FMTS + DEEP_PIX_FMTS + DEEP444_PIX_FMTS
 
 
 def add_input_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
@@ -157,7 +168,8 @@ def add_input_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--in-pix-fmt", type=str, default="rgb24", choices=list(IN_PIX_FMTS),
                    help="format of the frames read: raw rgb24 (default), or planar yuv420p / semi-planar nv12 converted on the GPU (1.5 bytes per pixel); "
                         "planar yuv422p / packed yuyv422 / uyvy422 (2 bytes per pixel); "
-                        "yuv420p10le / p010le (3 bytes per pixel) with a 10-bit --out-pix-fmt: the chain then runs on half pixels")
+                        "yuv420p10le / p010le (3 bytes per pixel) or yuv444p10le / gbrp10le (6) / x2rgb10le (4) with a 10-bit --out-pix-fmt: the chain "
+                        "then runs on half pixels")
     p.add_argument("--in-matrix", type=str, default="bt601", choices=["bt601", "bt709"], help="yuv420p / nv12 / 4:2:2 input: the Y'CbCr -> RGB matrix")
     p.add_argument("--in-range", type=str, default="tv", choices=["tv", "pc"], help="yuv420p / nv12 / 4:2:2 input: limited (tv, 16-235) or full (pc) range")
     return p
@@ -1010,13 +1022,14 @@ def main(argv=None) -> int:
             raise SystemExit("pass --input, --width and --height")
         return main_sharded(a, int(_os.environ.get("RANK", "0")), int(_os.environ.get("WORLD_SIZE", "1")))
     if a.gui or not a.input:
-        raise SystemExit("the GUI is not part of this path; pass --input (raw rgb24 / yuv420p / nv12 / yuv422p / yuyv422 / uyvy422 / yuv420p10le / p010le file or '-')")
+        raise SystemExit("the GUI is not part of this path; pass --input (raw rgb24 / yuv420p / nv12 / yuv422p / yuyv422 / uyvy422 / yuv420p10le / p010le / yuv444p10le / gbrp10le / x2rgb10le file or '-')")
     if a.width <= 0 or a.height <= 0:
         raise SystemExit("raw input needs --width and --height")
-    deep = a.in_pix_fmt in DEEP_PIX_FMTS
-    if deep != (a.out_pix_fmt in DEEP_PIX_FMTS):
+    deep = a.in_pix_fmt in DEEP_PIX_FMTS + DEEP444_PIX_FMTS
+    if deep != (a.out_pix_fmt in DEEP_PIX_FMTS + DEEP444_PIX_FMTS):
         raise SystemExit(f"--in-pix-fmt {a.in_pix_fmt} with --out-pix-fmt {a.out_pix_fmt}: a 10-bit format on one end only; the chain between them "
-                         "runs on half pixels or on uint8 ones — pass yuv420p10le / p010le on both ends or on neither")
+                         "runs on half pixels or on uint8 ones — pass yuv420p10le / p010le (or yuv444p10le / gbrp10le / x2rgb10le) on both ends "
+                         "or on neither")
     import os
     t_start = time.perf_counter()
     import torch
@@ -1031,7 +1044,7 @@ def main(argv=None) -> int:
     dev = torch.device("cuda", torch.cuda.current_device())
     seed = a.noise_seed if a.noise_seed is not None else int.from_bytes(os.urandom(8), "little")
     overlay = make_text_overlay_rgba(w, h, a.text, a.text_font, a.text_size, a.text_color, (a.text_x, a.text_y)) if a.text else None   # ref:1076
-    pix = torch.float16 if deep else torch.uint8                   # 10-bit 4:2:0 on both ends: the chain runs on half pixels (include/crtfx_deep.h)
+    pix = torch.float16 if deep else torch.uint8                   # 10-bit formats on both ends: the chain runs on half pixels (include/crtfx_deep.h, crtfx_444.h)
     pipe = FramePipeline(dev, h, w, rs, fps=fps_out, noise_seed=seed, dtype=pix, text_overlay_rgba=overlay, text_overlay_after=bool(a.text_after))
     t_engine = time.perf_counter() - t_start - t_imports
     fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb", buffering=0)
@@ -1042,7 +1055,9 @@ def main(argv=None) -> int:
     # and pinned output slots, the download, the output file's offsets and size — is in frames of out_bytes instead of frame_bytes
     egress = None
     if a.out_pix_fmt != "rgb24":
-        if deep:
+        if a.out_pix_fmt in DEEP444_PIX_FMTS:
+            from .deep444 import EgressDeep444 as EgressYuv
+        elif deep:
             from .deep import EgressYuv10 as EgressYuv
         elif a.out_pix_fmt in YUV422_PIX_FMTS:
             from .yuv422 import EgressYuv422 as EgressYuv
@@ -1056,7 +1071,9 @@ def main(argv=None) -> int:
     # frames of in_bytes instead of frame_bytes
     unpack = None
     if a.in_pix_fmt != "rgb24":
-        if deep:
+        if a.in_pix_fmt in DEEP444_PIX_FMTS:
+            from .deep444 import UnpackDeep444 as UnpackYuv
+        elif deep:
             from .deep import UnpackYuv10 as UnpackYuv
         elif a.in_pix_fmt in YUV422_PIX_FMTS:
             from .yuv422 import UnpackYuv422 as UnpackYuv

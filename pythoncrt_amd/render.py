@@ -23,6 +23,7 @@ import numpy as np
 # process_video keywords that belong to its container / codec plumbing (out of scope): accepted so that a caller can forward its
 # own keyword dictionary unchanged, and ignored
 _DEEP_FMTS = ("yuv420p10le", "p010le")          # the 10-bit 4:2:0 formats: both ends or neither (process_frames)
+_DEEP444_FMTS = ("yuv444p10le", "gbrp10le", "x2rgb10le")   # the 10-bit 4:4:4 formats: members of the 10-bit family, any pairing with it
 _422_FMTS = ("yuv422p", "yuyv422", "uyvy422")   # the 8-bit 4:2:2 formats: members of the 8-bit family, either end
 _IO_KEYS = ("input_path", "output_path", "width", "height", "fps", "crf", "target_bitrate_kbps", "gpu", "nvenc_preset", "encoder_preference",
             "decoder_preference")
@@ -86,6 +87,24 @@ def iter_yuv422(stream, w: int, h: int, layout: str):
         yield np.frombuffer(buf, dtype=np.uint8)
 
 
+def iter_deep444(stream, w: int, h: int, fmt: str):
+    """`iter_yuv422` for an already open byte stream of raw yuv444p10le, gbrp10le or x2rgb10le (`-f rawvideo -pix_fmt gbrp10le -`): 1-D uint8
+    arrays of deep444.frame_bytes(h, w, fmt) bytes — what `process_frames(..., in_pix_fmt=fmt)` takes — until the stream ends; the same
+    short-read handling, a trailing partial frame is dropped.  The bytes are not interpreted here."""
+    from .deep444 import frame_bytes
+    frame_size = frame_bytes(int(h), int(w), fmt)
+    while True:
+        buf = stream.read(frame_size)
+        while buf and len(buf) < frame_size:           # a pipe may return less than asked for: keep reading until the frame is whole or the stream ends
+            more = stream.read(frame_size - len(buf))
+            if not more:
+                break
+            buf += more
+        if not buf or len(buf) < frame_size:
+            return
+        yield np.frombuffer(buf, dtype=np.uint8)
+
+
 def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.ndarray], None], out_w: int, out_h: int, fps_out: float,
                    total_frames: Optional[int] = None, *,
                    scanline_strength: float = 0.6, triad_strength: float = 0.35, triad_gamma: float = 2.2, triad_preserve_luma: bool = False,
@@ -131,7 +150,12 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     pixels (FramePipeline(dtype=torch.float16)), UnpackYuv10 stands in front of it and EgressYuv10 behind it (include/crtfx_deep.h, same
     matrix and range keywords), items of `frame_iter` and the arrays handed to `write_frame` are 1-D uint8 arrays of
     2 * (h * w + 2 * ceil(h / 2) * ceil(w / 2)) bytes (`iter_yuv420(..., bits=10)` yields them; 16-bit arrays of half as many words are
-    taken too).  Refused with ValueError before a device is touched: a 10-bit format on one end only (the 8-bit stages have no half path,
+    taken too).  "yuv444p10le", "gbrp10le" and "x2rgb10le" (10-bit 4:4:4: ProRes 4444 / DNxHR 444 decodes, image sequences, screen capture)
+    are members of the same 10-bit family, in any pairing with it ("p010le" in with "x2rgb10le" out is allowed): UnpackDeep444 stands in
+    front of the half chain and EgressDeep444 behind it (include/crtfx_444.h), items of `frame_iter` (`iter_deep444` yields them) and the
+    arrays handed to `write_frame` are 1-D uint8 arrays of deep444.frame_bytes(h, w, fmt) bytes — 6 per pixel, 4 for x2rgb10le; 16-bit and
+    32-bit arrays of the same bytes are taken too.  The matrix and range keywords apply to yuv444p10le; gbrp10le and x2rgb10le are
+    full-range RGB and ignore them.  Refused with ValueError before a device is touched: a 10-bit format on one end only (the 8-bit stages have no half path,
     the 10-bit ones no uint8 path), `in_size` other than the output size (IngestResize has no half path), `resize_on="host"`.
     If `frame_iter` or `write_frame` raises, the GPU work already queued is drained (device synchronize) before the exception leaves this
     function, so that the staging buffers are not freed under a running copy."""
@@ -143,14 +167,14 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         raise TypeError(f"process_frames() got unexpected keyword arguments {sorted(unknown)}")
     if resize_on not in ("device", "host"):
         raise ValueError(f"resize_on must be 'device' or 'host', got {resize_on!r}")
-    if out_pix_fmt not in ("rgb24", "yuv420p", "nv12") + _422_FMTS + _DEEP_FMTS:
+    if out_pix_fmt not in ("rgb24", "yuv420p", "nv12") + _422_FMTS + _DEEP_FMTS + _DEEP444_FMTS:
         raise ValueError("out_pix_fmt must be 'rgb24', 'yuv420p' or 'nv12', 'yuv422p', 'yuyv422' or 'uyvy422' (or, with a 10-bit input, "
-                         f"'yuv420p10le' or 'p010le'), got {out_pix_fmt!r}")
-    if in_pix_fmt not in ("rgb24", "yuv420p", "nv12") + _422_FMTS + _DEEP_FMTS:
+                         f"'yuv420p10le' or 'p010le', 'yuv444p10le', 'gbrp10le' or 'x2rgb10le'), got {out_pix_fmt!r}")
+    if in_pix_fmt not in ("rgb24", "yuv420p", "nv12") + _422_FMTS + _DEEP_FMTS + _DEEP444_FMTS:
         raise ValueError("in_pix_fmt must be 'rgb24', 'yuv420p' or 'nv12', 'yuv422p', 'yuyv422' or 'uyvy422' (or, with a 10-bit output, "
-                         f"'yuv420p10le' or 'p010le'), got {in_pix_fmt!r}")
-    deep = in_pix_fmt in _DEEP_FMTS
-    if deep != (out_pix_fmt in _DEEP_FMTS):
+                         f"'yuv420p10le' or 'p010le', 'yuv444p10le', 'gbrp10le' or 'x2rgb10le'), got {in_pix_fmt!r}")
+    deep = in_pix_fmt in _DEEP_FMTS + _DEEP444_FMTS
+    if deep != (out_pix_fmt in _DEEP_FMTS + _DEEP444_FMTS):
         raise ValueError(f"in_pix_fmt={in_pix_fmt!r} with out_pix_fmt={out_pix_fmt!r}: a 10-bit format on one end only — the chain between "
                          "them runs on half pixels or on uint8 ones, and the 8-bit stages have no half path (the 10-bit ones no uint8 path)")
     if deep and in_size is not None and (int(in_size[0]), int(in_size[1])) != (int(out_h), int(out_w)):
@@ -187,7 +211,9 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
               for _ in range(NS)]
     egress = None
     if out_pix_fmt != "rgb24":                                                 # the encoder's format: converted on the device, half the bytes downloaded
-        if deep:
+        if out_pix_fmt in _DEEP444_FMTS:
+            from .deep444 import EgressDeep444 as EgressYuv
+        elif deep:
             from .deep import EgressYuv10 as EgressYuv
         elif out_pix_fmt in _422_FMTS:
             from .yuv422 import EgressYuv422 as EgressYuv
@@ -232,6 +258,9 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     if in_pix_fmt in _422_FMTS:
         from .yuv422 import frame_bytes as _bytes422
         yuv_bytes = _bytes422(yuv_hw[0], yuv_hw[1], in_pix_fmt)
+    elif in_pix_fmt in _DEEP444_FMTS:
+        from .deep444 import frame_bytes as _bytes444
+        yuv_bytes = _bytes444(yuv_hw[0], yuv_hw[1], in_pix_fmt)
     else:
         yuv_bytes = (yuv_hw[0] * yuv_hw[1] + 2 * ((yuv_hw[0] + 1) // 2) * ((yuv_hw[1] + 1) // 2)) * (2 if deep else 1)
 
@@ -239,7 +268,9 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         """Staging of a 4:2:0 or 4:2:2 input: pinned and device slots of frame_bytes(*in_size) bytes per frame, the plan that converts them to RGB —
         into dev_in[d] itself, or, where in_size is not the output size, into RGB slots of that size which IngestResize brings to dev_in[d]."""
         def __init__(self):
-            if deep:
+            if in_pix_fmt in _DEEP444_FMTS:
+                from .deep444 import UnpackDeep444 as UnpackYuv
+            elif deep:
                 from .deep import UnpackYuv10 as UnpackYuv
             elif in_pix_fmt in _422_FMTS:
                 from .yuv422 import UnpackYuv422 as UnpackYuv
@@ -281,7 +312,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         a = np.asarray(frame)
         if in_pix_fmt != "rgb24":
             a = a.reshape(-1)
-            if deep and a.dtype.itemsize == 2:       # 16-bit words: the same bytes
+            if deep and a.dtype.itemsize in (2, 4):  # 16-bit (or x2rgb10le's 32-bit) words: the same bytes
                 a = np.ascontiguousarray(a).view(np.uint8)
             if a.size != yuv_bytes:
                 raise ValueError(f"a {in_pix_fmt} frame of {yuv_hw[0]} x {yuv_hw[1]} holds {yuv_bytes} bytes, got an item of {a.size}")

@@ -373,3 +373,24 @@ def rgb_matrix10(matrix: str = "bt601", rng: str = "tv"):
     m = np.floor(f * 65536.0 + 0.5).astype(np.int64)
     off = np.array([64 if rng == "tv" else 0, 512, 512], dtype=np.int32)
     return np.ascontiguousarray(m.reshape(9).astype(np.int32)), off
+
+
+_RGB10_IN, _RGB10_OUT = 65344, 65729       # floor(1020/1023 * 65536 + 0.5), floor(1023/1020 * 65536 + 0.5)
+_RGB10_ORDERS = {"gbr": (1, 2, 0), "rgb": (0, 1, 2)}      # the RGB channel held by plane / field j
+
+
+def rgb_scale10(order: str = "rgb"):
+    """The tables of the two full-range RGB formats of the 10-bit 4:4:4 stages (include/crtfx_444.h) as the pair
+    ((m, off) of the source stage, (m, off) of the egress stage), each (m int32[9], off int32[3]) with off = 0: one constant on a
+    permuted diagonal.  `order` names the channel of plane / field j: "gbr" (gbrp10le: planes G, B, R) or "rgb" (x2rgb10le: fields R, G, B).
+    Source rows R, G, B over the columns P0, P1, P2 carry K = 65344 = floor(1020/1023 * 65536 + 0.5), the Y entry of
+    rgb_matrix10(., "pc"): 10-bit code 1023 gives quarter code 1020.  Egress rows T0, T1, T2 over the columns R, G, B carry
+    K' = 65729 = floor(1023/1020 * 65536 + 0.5), the Y-row sum of yuv_matrix10(., "pc"): quarter code 1020 gives 1023."""
+    if order not in _RGB10_ORDERS:
+        raise ValueError(f"order must be one of {sorted(_RGB10_ORDERS)}, got {order!r}")
+    src, egr = np.zeros((3, 3), dtype=np.int32), np.zeros((3, 3), dtype=np.int32)
+    for j, ch in enumerate(_RGB10_ORDERS[order]):
+        src[ch, j] = _RGB10_IN
+        egr[j, ch] = _RGB10_OUT
+    return ((np.ascontiguousarray(src.reshape(9)), np.zeros(3, dtype=np.int32)),
+            (np.ascontiguousarray(egr.reshape(9)), np.zeros(3, dtype=np.int32)))
