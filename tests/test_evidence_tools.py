@@ -282,6 +282,46 @@ def test_every_warp_build_has_a_gpu_sweep_row():
     assert len(warp_builds.covered_instances()) == 33
 
 
+def point_inventory(lib_path):
+    """(k_point* / k_half* instances in the library that no row of tests/point_builds.ROWS names, instances a row names that the library lacks)."""
+    import kernel_resources
+    from tests import point_builds
+    have = point_builds.library_instances(kernel_resources.resources(lib_path))
+    want = point_builds.covered_instances()
+    return sorted(have - want), sorted(want - have)
+
+
+def test_every_pointwise_build_has_a_gpu_sweep_row():
+    """Every crtfx::k_point*<...> and crtfx::k_half*<...> instance compiled into libcrtfx.so (60 k_point_fused_seq, 28 k_point_lean_seq, 8
+    k_point_lean, 4 k_point_sel, 4 k_point_sel_seq, k_point<runtime>, 5 k_half and 5 k_half_group) is named by a row of the table
+    tests/test_point_builds_gpu.py holds to the oracle, and every row names an instance the library has: an instantiation added to crtfx.hip
+    fails here, on the CPU, until the GPU sweep reaches it."""
+    from pythoncrt_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build()
+    uncovered, missing = point_inventory(_lib.LIB_PATH)
+    assert not uncovered, f"pointwise builds with no row in tests/point_builds.ROWS: {uncovered}"
+    assert not missing, f"rows of tests/point_builds.ROWS naming builds the library lacks: {missing}"
+    from tests import point_builds
+    assert len(point_builds.covered_instances()) == 115
+
+
+def test_pointwise_sf_words_come_from_the_sources():
+    from tests import point_builds
+    w = point_builds.sf_words()
+    flags = {k: v for k, v in w.items() if k.startswith("CRTFX_F_")}
+    kf = {k: v for k, v in w.items() if k.startswith("KF_")}
+    assert len(flags) == 16 and len(kf) == 5
+    assert w["SF_FAST_PIX"] == w["SF_FAST"] | w["CRTFX_F_PIXELATE"] and w["SF_FAST"] == w["SF_FULL_GATES"] | w["CRTFX_F_BLOOM_FAST"]
+    every = list(flags.values()) + list(kf.values())
+    assert all(v and v & (v - 1) == 0 for v in every) and len(set(every)) == len(every)      # single bits, all distinct: no KF_* on a CRTFX_F_* bit
+    assert not w["SF_FAST_PIX"] & (w["KF_GRADE_RT"] | w["KF_GRADE_LUT"] | w["KF_COARSE"] | w["KF_SCANPLANE"])
+    assert w["SF_LEAN_RT"] not in (w["SF_RUNTIME"], w["SF_FAST"], w["SF_FAST_PIX"]) and w["SF_RUNTIME"] == 0xFFFFFFFF
+    assert w["GRADE_RT_MASK"] & w["SF_FAST_PIX"] == 0 and sorted(w["KNOBS"]) == sorted(["+sat", "+luma", "+flicker", "-grain", "-vignette", "-triad", "-scanlines"])
+    words = [x for pair in point_builds.gate_names().values() for x in pair] + [w["SF_LEAN_RT"]]
+    assert len(set(words)) == len(words)                                                        # every gate name its own template word
+
+
 def test_phosphor_sf_words_come_from_the_sources():
     from tests import radius_builds
     w = radius_builds.sf_words()

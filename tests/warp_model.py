@@ -16,7 +16,12 @@ own functions composed with them and contains no arithmetic of its own:
     state, the half frame np.abs(state32 * float32(255)).astype(float16);
   * preview commit: orc.add_weighted on the float32-held state, the same narrowing.
 
+point_render is the same composition for the pointwise chain (no warp, fast or no bloom: tests/point_builds.py), where no pre-warp image is
+parked: the image reaches the blend un-narrowed, in the reference's own dtype, and only the state is float32.
+
 Only numpy and the oracle: nothing here imports torch or the package."""
+import contextlib
+
 import numpy as np
 
 from oracle import crt_oracle as orc
@@ -43,11 +48,32 @@ def promoted(cfg):
     return cfg.get("vignette_strength", 0.0) > 0.0 or (cfg.get("flicker_strength", 0.0) > 0.0 and cfg.get("flicker_hz", 0.0) > 0.0)
 
 
+# the keywords of the pointwise chain's settings (tests/point_builds.py): the colour grade, flicker, coarse grain, the 2-D scanline plane
+POINT_KEYS = ("brightness", "contrast", "gamma", "saturation", "temperature", "flicker_strength", "flicker_hz", "grain_size", "scanline_angle",
+              "scanline_thickness")
+
+
 def _params(cfg, **over):
     p = {k: cfg[k] for k in PARAM_KEYS}
-    p.update({k: cfg[k] for k in ("flicker_strength", "flicker_hz", "glitch_amp_px", "glitch_height_frac") if k in cfg})
+    p.update({k: cfg[k] for k in POINT_KEYS + ("glitch_amp_px", "glitch_height_frac") if k in cfg})
     p.update(over)
     return p
+
+
+@contextlib.contextmanager
+def injected_scan_plane(plane):
+    """The oracle's chain with its 2-D scanline mask (make_scanline_mask_2d: float64 sin / pow, returned float32) replaced by `plane`, the
+    float32 mask the GPU generated (crtfx_scanline_plane, held to the oracle's within one ulp by tests/test_parity_gpu.py) — an input handed
+    in, as the grain planes are; None: the oracle's own mask."""
+    if plane is None:
+        yield
+        return
+    own = orc.make_scanline_mask_2d
+    orc.make_scanline_mask_2d = lambda h, w, *a: np.ascontiguousarray(plane, np.float32).reshape(h, w)
+    try:
+        yield
+    finally:
+        orc.make_scanline_mask_2d = own
 
 
 def oracle_render(frames, cfg, fps=30.0, first=0, planes=None, state=None):
@@ -62,16 +88,18 @@ def oracle_render(frames, cfg, fps=30.0, first=0, planes=None, state=None):
     return outs, states
 
 
-def pre_images(frames, cfg, fps=30.0, first=0, planes=None):
+def pre_images(frames, cfg, fps=30.0, first=0, planes=None, scan_planes=None, parked=True):
     """The pre-warp image of every frame as the GPU holds it: the oracle's chain with warp, glitch and persistence off, narrowed to float32;
-    widened back to float64 when the chain is promoted."""
+    widened back to float64 when the chain is promoted.  scan_planes: per-frame 2-D scanline masks to hand in (injected_scan_plane).
+    parked=False: the image in the oracle's own dtype, never narrowed (the pointwise chain: see point_render)."""
     off = dict(cfg, warp_strength=0.0, persistence=0.0, glitch_amp_px=0, glitch_height_frac=0.0)
     out = []
     for j, f in enumerate(frames):
-        _, st = orc.process_frames([f], _params(off), fps, off["scanline_speed_px_s"], 0.0, off["triad_strength"], off["triad_softness"],
-                                   off["vignette_strength"], noise_planes=None if planes is None else [planes[j]], first_index=first + j)
+        with injected_scan_plane(None if scan_planes is None else scan_planes[j]):
+            _, st = orc.process_frames([f], _params(off), fps, off["scanline_speed_px_s"], 0.0, off["triad_strength"], off["triad_softness"],
+                                       off["vignette_strength"], noise_planes=None if planes is None else [planes[j]], first_index=first + j)
         assert st.dtype == (np.float64 if promoted(cfg) else np.float32), (st.dtype, promoted(cfg))
-        out.append(st.astype(np.float32).astype(st.dtype))
+        out.append(st.astype(np.float32).astype(st.dtype) if parked else st)
     return out
 
 
@@ -117,14 +145,23 @@ def render_chain(images, persistence, state=None):
     return states
 
 
-def render(frames, cfg, half=False, fps=30.0, first=0, planes=None, state=None):
+def render(frames, cfg, half=False, fps=30.0, first=0, planes=None, state=None, scan_planes=None, parked=True):
     """FramePipeline.run under the model: -> (frames as uint8 / half, per-frame float32 states)."""
-    imgs = [warp(p, cfg["warp_strength"]) for p in pre_images(frames, cfg, fps, first, planes)]
+    imgs = [warp(p, cfg["warp_strength"]) for p in pre_images(frames, cfg, fps, first, planes, scan_planes, parked)]
     if cfg["persistence"] > 0.0:
         states = render_chain(imgs, cfg["persistence"], state)
     else:
         states = [i.astype(np.float32) for i in imgs]
     return [quantise(s, half) for s in states], states
+
+
+def point_render(frames, cfg, half=False, fps=30.0, first=0, planes=None, state=None, scan_planes=None):
+    """A render run of the pointwise chain (fast or no bloom, warp off) under the model.  Nothing parks a pre-warp image there: the pointwise
+    kernels blend the image in the dtype the reference has it in (float64 once the vignette or the flicker promotes), in registers —
+    st = (float)clip01(p * (T)st + q * v) — so the float32 storage of the STATE is the model's one rounding and the image is the oracle's
+    own, un-narrowed (render's default narrows it first: the float32 image k_warp_lean and the commit-only build read back)."""
+    assert float(cfg["warp_strength"]) == 0.0
+    return render(frames, cfg, half, fps, first, planes, state, scan_planes, parked=False)
 
 
 def preview_step(img, persistence, state=None):
