@@ -272,7 +272,7 @@ class FramePipeline:
 
 # ---------------------------------------------------------------------------------------
 # GPU engine for shard.ShardedRender: local scan = crtfx_process_batch from a zero
-# state, correction = crtfx_halo_correct_quantise per frame.
+# state, correction = crtfx_halo_correct_batch, one launch per 64 frames of a chunk.
 # ---------------------------------------------------------------------------------------
 
 class _LocalStates:
