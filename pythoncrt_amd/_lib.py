@@ -14,8 +14,9 @@ LIB_PATH = os.environ.get("CRTFX_LIB") or os.path.join(_HERE, "libcrtfx.so")   #
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = [os.path.join(CSRC, f) for f in ("crtfx.hip", "crtfx_rr.hip", "crtfx_kernels.hip.h", "crtfx_common.hip.h", "crtfx_blur.hip.h", "crtfx_point.hip.h",
                                                 "crtfx_phosphor.hip.h", "crtfx_phosphor_ct.hip.h", "crtfx_warp.hip.h", "crtfx_internal.h", "crtfx_ingest.hip",
-                                                "crtfx_egress.hip", "crtfx_unpack.hip", "crtfx_deep.hip", "crtfx_422.hip", "crtfx_444.hip")] + \
+                                                "crtfx_egress.hip", "crtfx_unpack.hip", "crtfx_deep.hip", "crtfx_422.hip", "crtfx_444.hip", "crtfx_stage_host.h")] + \
           [os.path.join(ROOT, "include", f) for f in ("crtfx.h", "crtfx_ingest.h", "crtfx_egress.h", "crtfx_unpack.h", "crtfx_deep.h", "crtfx_422.h", "crtfx_444.h")]
+STAGE_UNITS = ("crtfx_ingest", "crtfx_egress", "crtfx_unpack", "crtfx_deep", "crtfx_422", "crtfx_444")   # one object file each, beside crtfx.hip / crtfx_rr.hip
 RR_RADII = tuple(range(1, 31))      # one register-window build per radius up to 30 (crtfx_internal.h); larger radii: the split path
 
 OK, E_INVALID, E_HIP, E_UNSUPPORTED, E_NOMEM = 0, -1, -2, -3, -4
@@ -100,79 +101,47 @@ INGEST_SYMBOLS = {
     "crtfx_ingest_last_plan": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t]),
 }
 
+
+def stage_symbols(*families):
+    """The seven entry points of each crtfx_<family>_* family of format stages (include/crtfx_egress.h spells them out; pythoncrt_amd/_stage.py
+    is their one caller)."""
+    return {f"crtfx_{fam}_{name}": sig for fam in families for name, sig in (
+        ("create", (ctypes.c_int, [ctypes.c_int] * 5 + [_vp, _vp, ctypes.POINTER(_vp)])),
+        ("destroy", (ctypes.c_int, [_vp])),
+        ("last_error", (ctypes.c_char_p, [_vp])),
+        ("frame_bytes", (ctypes.c_size_t, [_vp])),
+        ("run", (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp])),
+        ("set_option", (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int])),
+        ("last_plan", (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t])))}
+
+
 # ... and every symbol include/crtfx_egress.h declares (the egress stage: a handle of its own, pythoncrt_amd/egress.py)
 EGRESS_YUV420P, EGRESS_NV12 = 0, 1
 EGRESS_OPT_FORCE_GENERAL = 1
-EGRESS_SYMBOLS = {
-    "crtfx_egress_create": (ctypes.c_int, [ctypes.c_int] * 5 + [_vp, _vp, ctypes.POINTER(_vp)]),
-    "crtfx_egress_destroy": (ctypes.c_int, [_vp]),
-    "crtfx_egress_last_error": (ctypes.c_char_p, [_vp]),
-    "crtfx_egress_frame_bytes": (ctypes.c_size_t, [_vp]),
-    "crtfx_egress_run": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
-    "crtfx_egress_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
-    "crtfx_egress_last_plan": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t]),
-}
+EGRESS_SYMBOLS = stage_symbols("egress")
 
 # ... and every symbol include/crtfx_unpack.h declares (the source stage: a handle of its own, pythoncrt_amd/unpack.py)
 UNPACK_YUV420P, UNPACK_NV12 = 0, 1
 UNPACK_OPT_FORCE_GENERAL = 1
-UNPACK_SYMBOLS = {
-    "crtfx_unpack_create": (ctypes.c_int, [ctypes.c_int] * 5 + [_vp, _vp, ctypes.POINTER(_vp)]),
-    "crtfx_unpack_destroy": (ctypes.c_int, [_vp]),
-    "crtfx_unpack_last_error": (ctypes.c_char_p, [_vp]),
-    "crtfx_unpack_frame_bytes": (ctypes.c_size_t, [_vp]),
-    "crtfx_unpack_run": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
-    "crtfx_unpack_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
-    "crtfx_unpack_last_plan": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t]),
-}
+UNPACK_SYMBOLS = stage_symbols("unpack")
 
 # ... and every symbol include/crtfx_deep.h declares (the 10-bit source and egress stages: two handle families, pythoncrt_amd/deep.py)
 DEEP_YUV420P10LE, DEEP_P010LE = 0, 1
 UNPACK10_OPT_FORCE_GENERAL = 1
 EGRESS10_OPT_FORCE_GENERAL = 1
-DEEP_SYMBOLS = {}
-for _fam in ("unpack10", "egress10"):
-    DEEP_SYMBOLS.update({
-        f"crtfx_{_fam}_create": (ctypes.c_int, [ctypes.c_int] * 5 + [_vp, _vp, ctypes.POINTER(_vp)]),
-        f"crtfx_{_fam}_destroy": (ctypes.c_int, [_vp]),
-        f"crtfx_{_fam}_last_error": (ctypes.c_char_p, [_vp]),
-        f"crtfx_{_fam}_frame_bytes": (ctypes.c_size_t, [_vp]),
-        f"crtfx_{_fam}_run": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
-        f"crtfx_{_fam}_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
-        f"crtfx_{_fam}_last_plan": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t]),
-    })
+DEEP_SYMBOLS = stage_symbols("unpack10", "egress10")
 
 # ... and every symbol include/crtfx_422.h declares (the 8-bit 4:2:2 source and egress stages: two handle families, pythoncrt_amd/yuv422.py)
 YUV422_YUV422P, YUV422_YUYV422, YUV422_UYVY422 = 0, 1, 2
 UNPACK422_OPT_FORCE_GENERAL = 1
 EGRESS422_OPT_FORCE_GENERAL = 1
-YUV422_SYMBOLS = {}
-for _fam in ("unpack422", "egress422"):
-    YUV422_SYMBOLS.update({
-        f"crtfx_{_fam}_create": (ctypes.c_int, [ctypes.c_int] * 5 + [_vp, _vp, ctypes.POINTER(_vp)]),
-        f"crtfx_{_fam}_destroy": (ctypes.c_int, [_vp]),
-        f"crtfx_{_fam}_last_error": (ctypes.c_char_p, [_vp]),
-        f"crtfx_{_fam}_frame_bytes": (ctypes.c_size_t, [_vp]),
-        f"crtfx_{_fam}_run": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
-        f"crtfx_{_fam}_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
-        f"crtfx_{_fam}_last_plan": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t]),
-    })
+YUV422_SYMBOLS = stage_symbols("unpack422", "egress422")
 
 # ... and every symbol include/crtfx_444.h declares (the 10-bit 4:4:4 source and egress stages: two handle families, pythoncrt_amd/deep444.py)
 DEEP444_PLANAR, DEEP444_X2RGB10LE = 0, 1
 UNPACK444_OPT_FORCE_GENERAL = 1
 EGRESS444_OPT_FORCE_GENERAL = 1
-DEEP444_SYMBOLS = {}
-for _fam in ("unpack444", "egress444"):
-    DEEP444_SYMBOLS.update({
-        f"crtfx_{_fam}_create": (ctypes.c_int, [ctypes.c_int] * 5 + [_vp, _vp, ctypes.POINTER(_vp)]),
-        f"crtfx_{_fam}_destroy": (ctypes.c_int, [_vp]),
-        f"crtfx_{_fam}_last_error": (ctypes.c_char_p, [_vp]),
-        f"crtfx_{_fam}_frame_bytes": (ctypes.c_size_t, [_vp]),
-        f"crtfx_{_fam}_run": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
-        f"crtfx_{_fam}_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
-        f"crtfx_{_fam}_last_plan": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t]),
-    })
+DEEP444_SYMBOLS = stage_symbols("unpack444", "egress444")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC"]
 
@@ -192,12 +161,8 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), out: str =
     for r in RR_RADII:
         jobs.append([hipcc, *HIPCC_FLAGS, *extra_flags, *inc, f"-DRR_R={r}", "-c", os.path.join(CSRC, "crtfx_rr.hip"),
                      "-o", os.path.join(objdir, f"crtfx_rr_{r}.o")])
-    jobs.append([hipcc, *HIPCC_FLAGS, *extra_flags, *inc, "-c", os.path.join(CSRC, "crtfx_ingest.hip"), "-o", os.path.join(objdir, "crtfx_ingest.o")])
-    jobs.append([hipcc, *HIPCC_FLAGS, *extra_flags, *inc, "-c", os.path.join(CSRC, "crtfx_egress.hip"), "-o", os.path.join(objdir, "crtfx_egress.o")])
-    jobs.append([hipcc, *HIPCC_FLAGS, *extra_flags, *inc, "-c", os.path.join(CSRC, "crtfx_unpack.hip"), "-o", os.path.join(objdir, "crtfx_unpack.o")])
-    jobs.append([hipcc, *HIPCC_FLAGS, *extra_flags, *inc, "-c", os.path.join(CSRC, "crtfx_deep.hip"), "-o", os.path.join(objdir, "crtfx_deep.o")])
-    jobs.append([hipcc, *HIPCC_FLAGS, *extra_flags, *inc, "-c", os.path.join(CSRC, "crtfx_422.hip"), "-o", os.path.join(objdir, "crtfx_422.o")])
-    jobs.append([hipcc, *HIPCC_FLAGS, *extra_flags, *inc, "-c", os.path.join(CSRC, "crtfx_444.hip"), "-o", os.path.join(objdir, "crtfx_444.o")])
+    for unit in STAGE_UNITS:
+        jobs.append([hipcc, *HIPCC_FLAGS, *extra_flags, *inc, "-c", os.path.join(CSRC, unit + ".hip"), "-o", os.path.join(objdir, unit + ".o")])
 
     def run(cmd):
         if verbose:
@@ -233,9 +198,8 @@ def build_variant(name: str, extra_flags, radii=(9,), main_tu: bool = False) -> 
         main = os.path.join(objdir, "crtfx.o")
         subprocess.run([hipcc, *HIPCC_FLAGS, *extra_flags, *inc, "-c", os.path.join(CSRC, "crtfx.hip"), "-o", main], check=True)
     out = os.path.join(ROOT, "build", "ab", f"libcrtfx_{name}.so")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out, main, *objs, os.path.join(base, "crtfx_ingest.o"),
-                    os.path.join(base, "crtfx_egress.o"), os.path.join(base, "crtfx_unpack.o"), os.path.join(base, "crtfx_deep.o"),
-                    os.path.join(base, "crtfx_422.o"), os.path.join(base, "crtfx_444.o")], check=True)
+    subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out, main, *objs,
+                    *(os.path.join(base, unit + ".o") for unit in STAGE_UNITS)], check=True)
     return out
 
 

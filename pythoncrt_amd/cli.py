@@ -76,6 +76,8 @@ import time
 
 import numpy as np
 
+from . import formats
+
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="pythoncrt_amd.cli", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -140,10 +142,10 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
-DEEP_PIX_FMTS = ("yuv420p10le", "p010le")     # 10-bit 4:2:0: on both ends or on neither (the chain then runs on half pixels)
-DEEP444_PIX_FMTS = ("yuv444p10le", "gbrp10le", "x2rgb10le")    # 10-bit 4:4:4: members of the 10-bit family, in any pairing with it
-YUV422_PIX_FMTS = ("yuv422p", "yuyv422", "uyvy422")    # 8-bit 4:2:2: members of the 8-bit family, either end independently of the other
-OUT_PIX_FMTS = ("rgb24", "yuv420p", "nv12") + YUV422_PIX_FMTS + DEEP_PIX_FMTS + DEEP444_PIX_FMTS
+# the accepted formats, from the registry (pythoncrt_amd/formats.py): a 10-bit format goes on both ends or on neither (the chain then runs
+# on half pixels); the 8-bit ones go on either end independently of the other
+DEEP_PIX_FMTS, DEEP444_PIX_FMTS, YUV422_PIX_FMTS = formats.DEEP420.names, formats.DEEP444.names, formats.YUV422.names
+OUT_PIX_FMTS = IN_PIX_FMTS = formats.PIX_FMTS
 
 
 def add_output_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
@@ -157,9 +159,6 @@ def add_output_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--out-matrix", type=str, default="bt601", choices=["bt601", "bt709"], help="yuv420p / nv12 / 4:2:2: the RGB -> Y'CbCr matrix")
     p.add_argument("--out-range", type=str, default="tv", choices=["tv", "pc"], help="yuv420p / nv12 / 4:2:2: limited (tv, 16-235) or full (pc) range")
     return p
-
-
-IN_PIX_FMTS = ("rgb24", "yuv420p", "nv12") + YUV422_PIX_FMTS + DEEP_PIX_FMTS + DEEP444_PIX_FMTS
 
 
 def add_input_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
@@ -1025,8 +1024,8 @@ def main(argv=None) -> int:
         raise SystemExit("the GUI is not part of this path; pass --input (raw rgb24 / yuv420p / nv12 / yuv422p / yuyv422 / uyvy422 / yuv420p10le / p010le / yuv444p10le / gbrp10le / x2rgb10le file or '-')")
     if a.width <= 0 or a.height <= 0:
         raise SystemExit("raw input needs --width and --height")
-    deep = a.in_pix_fmt in DEEP_PIX_FMTS + DEEP444_PIX_FMTS
-    if deep != (a.out_pix_fmt in DEEP_PIX_FMTS + DEEP444_PIX_FMTS):
+    deep = formats.bits(a.in_pix_fmt) == 10
+    if deep != (formats.bits(a.out_pix_fmt) == 10):
         raise SystemExit(f"--in-pix-fmt {a.in_pix_fmt} with --out-pix-fmt {a.out_pix_fmt}: a 10-bit format on one end only; the chain between them "
                          "runs on half pixels or on uint8 ones — pass yuv420p10le / p010le (or yuv444p10le / gbrp10le / x2rgb10le) on both ends "
                          "or on neither")
@@ -1055,15 +1054,7 @@ def main(argv=None) -> int:
     # and pinned output slots, the download, the output file's offsets and size — is in frames of out_bytes instead of frame_bytes
     egress = None
     if a.out_pix_fmt != "rgb24":
-        if a.out_pix_fmt in DEEP444_PIX_FMTS:
-            from .deep444 import EgressDeep444 as EgressYuv
-        elif deep:
-            from .deep import EgressYuv10 as EgressYuv
-        elif a.out_pix_fmt in YUV422_PIX_FMTS:
-            from .yuv422 import EgressYuv422 as EgressYuv
-        else:
-            from .egress import EgressYuv
-        egress = EgressYuv(dev, (h, w), layout=a.out_pix_fmt, matrix=a.out_matrix, range=a.out_range)
+        egress = formats.FORMATS[a.out_pix_fmt].egress(dev, (h, w), layout=a.out_pix_fmt, matrix=a.out_matrix, range=a.out_range)
     out_bytes = frame_bytes if egress is None else egress.frame_bytes
     out_shape = (B, h, w, 3) if egress is None else (B, out_bytes)
     # --in-pix-fmt yuv420p / nv12 / yuv422p / yuyv422 / uyvy422, the mirror image: the frames are converted to RGB on the device in front of the chain (UnpackYuv) and
@@ -1071,15 +1062,7 @@ def main(argv=None) -> int:
     # frames of in_bytes instead of frame_bytes
     unpack = None
     if a.in_pix_fmt != "rgb24":
-        if a.in_pix_fmt in DEEP444_PIX_FMTS:
-            from .deep444 import UnpackDeep444 as UnpackYuv
-        elif deep:
-            from .deep import UnpackYuv10 as UnpackYuv
-        elif a.in_pix_fmt in YUV422_PIX_FMTS:
-            from .yuv422 import UnpackYuv422 as UnpackYuv
-        else:
-            from .unpack import UnpackYuv
-        unpack = UnpackYuv(dev, (h, w), layout=a.in_pix_fmt, matrix=a.in_matrix, range=a.in_range)
+        unpack = formats.FORMATS[a.in_pix_fmt].source(dev, (h, w), layout=a.in_pix_fmt, matrix=a.in_matrix, range=a.in_range)
     in_bytes = frame_bytes if unpack is None else unpack.frame_bytes
     in_shape = (B, h, w, 3) if unpack is None else (B, in_bytes)
     t0 = time.perf_counter()

@@ -1,15 +1,13 @@
 // crtfx_444.hip — the 10-bit 4:4:4 pair of libcrtfx.so (include/crtfx_444.h): yuv444p10le / gbrp10le / x2rgb10le frames -> half RGB in front
 // of a half chain (crtfx_unpack444_*), finished half RGB frames -> the same layouts behind it (crtfx_egress444_*).  A translation unit of its
-// own: it shares no kernel, table or handle with the effect chain, the ingest stage or the other source and egress stages.
+// own: it shares no kernel, table or handle with the effect chain, the ingest stage or the other source and egress stages.  The host code around the kernels (checks, frame-group loop, error strings) is
+// the skeleton of crtfx_stage_host.h: host templates only, so nothing is shared at run time either.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdio>
-#include <cstring>
-#include <new>
-#include <string>
 
 #include "crtfx_444.h"
+#include "crtfx_stage_host.h"
 
 namespace crtfx_444_impl {
 
@@ -181,141 +179,23 @@ __global__ __launch_bounds__(BLOCK) void k_egress10_444(Args a) {
     }
 }
 
-// what the two handle families share: one plan structure, told apart by `egress`
-struct Plan {
-    bool egress = false;
-    int device = 0;
-    int layout = CRTFX_444_PLANAR;
-    Args args{};                        // launch constants (frame pointers filled per run)
-    size_t frame_bytes = 0;             // of the 10-bit side
-    size_t rgb_bytes = 0;               // of the half RGB side
-    bool force_general = false;
-    char plan[128] = "";
-    std::string err;
-};
+struct Plan : crtfx_stage::StagePlan { Args args{}; };         // what the two handle families share, told apart by `egress`
 
 }  // namespace crtfx_444_impl
 
 using namespace crtfx_444_impl;
+using namespace crtfx_stage;
 
 struct crtfx_unpack444 : Plan {};
 struct crtfx_egress444 : Plan {};
 
 namespace {
 
-thread_local std::string g_create_err[2];       // [0] source, [1] egress
-
-int fail(Plan* p, bool egress, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (p) p->err = buf; else g_create_err[egress] = buf;
-    return code;
-}
-
-struct DeviceGuard {
-    int prev = -1;
-    bool switched = false;
-    hipError_t err = hipSuccess;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) { err = hipSetDevice(dev); switched = err == hipSuccess; }
-    }
-    ~DeviceGuard() { if (switched && prev >= 0) (void)hipSetDevice(prev); }
-};
-
-// source: the accumulator of one row stays inside int32 for every input, |c_j| <= 1023
-bool source_row_fits(const int32_t* row) {
-    long long s = 1LL << (SH - 1);
-    for (int i = 0; i < 3; ++i) s += (row[i] < 0 ? -(long long)row[i] : (long long)row[i]) * 1023;
-    return s < (1LL << 31);
-}
-
-// egress: the accumulator of one row stays in [0, 2^31) for every input: constant + (negative entries) * 1020 >= 0, constant + (positive entries) * 1020 < 2^31
-bool egress_row_fits(const int32_t* row, long long konst) {
-    long long pos = 0, neg = 0;
-    for (int i = 0; i < 3; ++i) { if (row[i] > 0) pos += row[i]; else neg += row[i]; }
-    return konst + neg * 1020 >= 0 && konst + pos * 1020 < (1LL << 31);
-}
-
-bool vec_fits(const Plan* p, const void* src, size_t src_stride, const void* dst, size_t dst_stride, int n) {
-    if (p->force_general || (p->args.w & 7)) return false;
-    if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 3u) return false;
-    return n <= 1 || !((src_stride | dst_stride) & 3u);
-}
-
-void note_plan(Plan* p, bool vec, int frames) {
-    const char* name = p->egress ? "egress444=k_egress10_444" : "unpack444=k_unpack10_444";
-    snprintf(p->plan, sizeof p->plan, "%s<%s,%s>;frames=%d", name, p->layout == CRTFX_444_X2RGB10LE ? "x2rgb10le" : "planar", vec ? "vec" : "general", frames);
-}
-
-template <class H>
-int create(bool egress, int device, int h, int w, int pix_fmt, int layout, const int32_t* m, const int32_t* off, H** out_plan) {
-    g_create_err[egress].clear();
-    if (!out_plan) return fail(nullptr, egress, CRTFX_E_INVALID, "out_plan is null");
-    *out_plan = nullptr;
-    if (pix_fmt == CRTFX_PIX_U8)
-        return fail(nullptr, egress, CRTFX_E_UNSUPPORTED, "only half RGB frames are %s (the 10-bit 4:4:4 stages have no uint8 path)", egress ? "converted" : "written");
-    if (pix_fmt != CRTFX_PIX_F16) return fail(nullptr, egress, CRTFX_E_INVALID, "unknown pixel format %d", pix_fmt);
-    if (h < 1 || w < 1 || h > 32767 || w > 32767) return fail(nullptr, egress, CRTFX_E_INVALID, "size %dx%d outside 1..32767", h, w);
-    if (layout != CRTFX_444_PLANAR && layout != CRTFX_444_X2RGB10LE) return fail(nullptr, egress, CRTFX_E_INVALID, "unknown layout %d", layout);
-    if (!m || !off) return fail(nullptr, egress, CRTFX_E_INVALID, "a table is null");
-    for (int i = 0; i < 3; ++i)
-        if (off[i] < 0 || off[i] > 1023) return fail(nullptr, egress, CRTFX_E_INVALID, "offset %d = %d outside 0..1023", i, off[i]);
-    long long k[3] = {off[0], off[1], off[2]};
-    if (egress) {
-        for (int i = 0; i < 3; ++i) {
-            k[i] = ((long long)off[i] << SH) + (1LL << (SH - 1));
-            if (!egress_row_fits(m + 3 * i, k[i])) return fail(nullptr, egress, CRTFX_E_INVALID, "the matrix lets an accumulator leave [0, 2^31)");
-        }
-    } else if (!source_row_fits(m) || !source_row_fits(m + 3) || !source_row_fits(m + 6)) {
-        return fail(nullptr, egress, CRTFX_E_INVALID, "the matrix lets an accumulator leave int32");
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(nullptr, egress, CRTFX_E_HIP, "no HIP device %d", device);
-    DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return fail(nullptr, egress, CRTFX_E_HIP, "hipSetDevice(%d): %s", device, hipGetErrorString(guard.err));
-    H* p = new (std::nothrow) H();
-    if (!p) return fail(nullptr, egress, CRTFX_E_NOMEM, "out of host memory");
-    p->egress = egress; p->device = device; p->layout = layout;
-    Args& a = p->args;
-    a.h = h; a.w = w;
-    for (int i = 0; i < 9; ++i) a.m[i] = m[i];
-    for (int i = 0; i < 3; ++i) a.k[i] = (int)k[i];
-    p->frame_bytes = (size_t)h * w * (layout == CRTFX_444_X2RGB10LE ? 4 : 6);
-    p->rgb_bytes = (size_t)h * w * 6;
-    note_plan(p, vec_fits(p, nullptr, 0, nullptr, 0, 1), 0);
-    *out_plan = p;
-    return CRTFX_OK;
-}
-
-int destroy(Plan* p) {
-    if (!p) return CRTFX_OK;
-    DeviceGuard guard(p->device);
-    (void)hipDeviceSynchronize();
-    return CRTFX_OK;
-}
-
-int set_option(Plan* p, int option, int value) {
-    if (!p) return CRTFX_E_INVALID;
-    static_assert((int)CRTFX_UNPACK444_OPT_FORCE_GENERAL == (int)CRTFX_EGRESS444_OPT_FORCE_GENERAL, "one option number for both families");
-    if (option != CRTFX_UNPACK444_OPT_FORCE_GENERAL) return fail(p, p->egress, CRTFX_E_INVALID, "unknown %s option %d", p->egress ? "egress444" : "unpack444", option);
-    if (value != 0 && value != 1) return fail(p, p->egress, CRTFX_E_INVALID, "FORCE_GENERAL takes 0 or 1, got %d", value);
-    p->force_general = value != 0;
-    note_plan(p, vec_fits(p, nullptr, 0, nullptr, 0, 1), 0);
-    return CRTFX_OK;
-}
-
-int last_plan(Plan* p, char* buf, size_t n) {
-    if (!p || !buf || n == 0) return CRTFX_E_INVALID;
-    snprintf(buf, n, "%s", p->plan);
-    return CRTFX_OK;
-}
+static_assert(SH == MATRIX_SH, "the row checks of crtfx_stage_host.h assume this matrix scale");
+static_assert((int)CRTFX_UNPACK444_OPT_FORCE_GENERAL == (int)CRTFX_EGRESS444_OPT_FORCE_GENERAL, "one option number for both families");
 
 template <int LAYOUT>
-void launch(const Plan* p, bool vec, dim3 grid, hipStream_t st, const Args& a) {
+void launch_layout(const Plan* p, bool vec, dim3 grid, hipStream_t st, const Args& a) {
     if (p->egress) {
         if (vec) hipLaunchKernelGGL((k_egress10_444<LAYOUT, VEC>), grid, dim3(BLOCK), 0, st, a);
         else hipLaunchKernelGGL((k_egress10_444<LAYOUT, GENERAL>), grid, dim3(BLOCK), 0, st, a);
@@ -325,42 +205,54 @@ void launch(const Plan* p, bool vec, dim3 grid, hipStream_t st, const Args& a) {
     }
 }
 
-int run(Plan* p, const void* src_base, size_t src_stride_bytes, void* dst_base, size_t dst_stride_bytes, int n, void* stream) {
-    if (!p) return CRTFX_E_INVALID;
-    if (!src_base || !dst_base) return fail(p, p->egress, CRTFX_E_INVALID, "null frame pointer");
-    if (n < 1) return fail(p, p->egress, CRTFX_E_INVALID, "n = %d frames", n);
+struct Unit {
+    static constexpr int block = BLOCK, force_option = CRTFX_UNPACK444_OPT_FORCE_GENERAL;
+    static const char* name(bool egress) { return egress ? "egress444" : "unpack444"; }
+    static void note_plan(Plan* p, bool vec, int frames) {
+        const char* kernel = p->egress ? "egress444=k_egress10_444" : "unpack444=k_unpack10_444";
+        snprintf(p->plan, sizeof p->plan, "%s<%s,%s>;frames=%d", kernel, p->layout == CRTFX_444_X2RGB10LE ? "x2rgb10le" : "planar", vec ? "vec" : "general", frames);
+    }
     // the half side holds 16-bit words; the 10-bit side 16-bit (planar) or 32-bit (x2rgb10le) ones
-    const uintptr_t rgb_side = p->egress ? reinterpret_cast<uintptr_t>(src_base) | src_stride_bytes : reinterpret_cast<uintptr_t>(dst_base) | dst_stride_bytes;
-    const uintptr_t deep_side = p->egress ? reinterpret_cast<uintptr_t>(dst_base) | dst_stride_bytes : reinterpret_cast<uintptr_t>(src_base) | src_stride_bytes;
-    if (rgb_side & 1u) return fail(p, p->egress, CRTFX_E_INVALID, "an odd half-frame base or stride: 16-bit samples need 2-byte alignment");
-    if (p->layout == CRTFX_444_X2RGB10LE) {
-        if (deep_side & 3u) return fail(p, p->egress, CRTFX_E_INVALID, "an x2rgb10le frame base or stride is no multiple of 4: 32-bit words need 4-byte alignment");
-    } else if (deep_side & 1u) {
-        return fail(p, p->egress, CRTFX_E_INVALID, "an odd planar frame base or stride: 16-bit samples need 2-byte alignment");
+    static int check_alignment(Plan* p, const void* src_base, size_t src_stride_bytes, const void* dst_base, size_t dst_stride_bytes) {
+        const uintptr_t rgb_side = p->egress ? reinterpret_cast<uintptr_t>(src_base) | src_stride_bytes : reinterpret_cast<uintptr_t>(dst_base) | dst_stride_bytes;
+        const uintptr_t deep_side = p->egress ? reinterpret_cast<uintptr_t>(dst_base) | dst_stride_bytes : reinterpret_cast<uintptr_t>(src_base) | src_stride_bytes;
+        if (rgb_side & 1u) return fail(p, CRTFX_E_INVALID, "an odd half-frame base or stride: 16-bit samples need 2-byte alignment");
+        if (p->layout == CRTFX_444_X2RGB10LE) {
+            if (deep_side & 3u) return fail(p, CRTFX_E_INVALID, "an x2rgb10le frame base or stride is no multiple of 4: 32-bit words need 4-byte alignment");
+        } else if (deep_side & 1u) {
+            return fail(p, CRTFX_E_INVALID, "an odd planar frame base or stride: 16-bit samples need 2-byte alignment");
+        }
+        return CRTFX_OK;
     }
-    const size_t src_bytes = p->egress ? p->rgb_bytes : p->frame_bytes, dst_bytes = p->egress ? p->frame_bytes : p->rgb_bytes;
-    if (n > 1 && (src_stride_bytes < src_bytes || dst_stride_bytes < dst_bytes))
-        return fail(p, p->egress, CRTFX_E_INVALID, "frame strides %zu / %zu bytes are smaller than a frame (%zu / %zu)", src_stride_bytes, dst_stride_bytes, src_bytes, dst_bytes);
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(p, p->egress, CRTFX_E_HIP, "hipGetDevice failed");
-    if (dev != p->device) return fail(p, p->egress, CRTFX_E_INVALID, "current device %d is not the plan's device %d (call hipSetDevice first)", dev, p->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint8_t* src = static_cast<const uint8_t*>(src_base);
-    uint8_t* dst = static_cast<uint8_t*>(dst_base);
-    const bool vec = vec_fits(p, src_base, src_stride_bytes, dst_base, dst_stride_bytes, n);
-    const int items = vec ? p->args.h * (p->args.w >> 3) : p->args.h * p->args.w;            // at most 32767 * 32767 < 2^30
-    const int group = 32768;                                                                 // grid.z
-    for (int f = 0; f < n; f += group) {
-        Args a = p->args;
-        a.src = src + (size_t)f * src_stride_bytes; a.src_stride = src_stride_bytes;
-        a.dst = dst + (size_t)f * dst_stride_bytes; a.dst_stride = dst_stride_bytes;
-        const dim3 grid((items + BLOCK - 1) / BLOCK, 1, n - f < group ? n - f : group);
-        if (p->layout == CRTFX_444_X2RGB10LE) launch<CRTFX_444_X2RGB10LE>(p, vec, grid, st, a);
-        else launch<CRTFX_444_PLANAR>(p, vec, grid, st, a);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(p, p->egress, CRTFX_E_HIP, "%s launch: %s", p->egress ? "egress444" : "unpack444", hipGetErrorString(e));
+    static int items(const Args& a, bool vec) { return vec ? a.h * (a.w >> 3) : a.h * a.w; }           // at most 32767 * 32767 < 2^30
+    static void launch(const Plan* p, bool vec, dim3 grid, hipStream_t st, const Args& a) {
+        if (p->layout == CRTFX_444_X2RGB10LE) launch_layout<CRTFX_444_X2RGB10LE>(p, vec, grid, st, a);
+        else launch_layout<CRTFX_444_PLANAR>(p, vec, grid, st, a);
     }
-    note_plan(p, vec, n);
+};
+
+template <class H>
+int create(bool egress, int device, int h, int w, int pix_fmt, int layout, const int32_t* m, const int32_t* off, H** out_plan) {
+    if (const int rc = begin_create(out_plan)) return rc;
+    if (pix_fmt == CRTFX_PIX_U8)
+        return fail<H>(nullptr, CRTFX_E_UNSUPPORTED, "only half RGB frames are %s (the 10-bit 4:4:4 stages have no uint8 path)", egress ? "converted" : "written");
+    if (const int rc = check_create<H>(pix_fmt, CRTFX_PIX_F16, h, w, layout, layout == CRTFX_444_PLANAR || layout == CRTFX_444_X2RGB10LE, m, off, CMAX)) return rc;
+    long long k[3] = {off[0], off[1], off[2]};
+    if (egress) {
+        for (int i = 0; i < 3; ++i) {
+            k[i] = ((long long)off[i] << SH) + (1LL << (SH - 1));
+            if (!egress_row_fits(m + 3 * i, k[i], QMAX)) return fail<H>(nullptr, CRTFX_E_INVALID, "the matrix lets an accumulator leave [0, 2^31)");
+        }
+    } else if (!source_row_fits(m, CMAX) || !source_row_fits(m + 3, CMAX) || !source_row_fits(m + 6, CMAX)) {
+        return fail<H>(nullptr, CRTFX_E_INVALID, "the matrix lets an accumulator leave int32");
+    }
+    H* p = nullptr;
+    if (const int rc = new_plan(egress, device, layout, h, w, m, &p)) return rc;
+    for (int i = 0; i < 3; ++i) p->args.k[i] = (int)k[i];
+    p->frame_bytes = (size_t)h * w * (layout == CRTFX_444_X2RGB10LE ? 4 : 6);
+    p->rgb_bytes = (size_t)h * w * 6;
+    Unit::note_plan(p, vec_fits(p, nullptr, 0, nullptr, 0, 1), 0);
+    *out_plan = p;
     return CRTFX_OK;
 }
 
@@ -368,28 +260,28 @@ int run(Plan* p, const void* src_base, size_t src_stride_bytes, void* dst_base, 
 
 extern "C" {
 
-const char* crtfx_unpack444_last_error(const crtfx_unpack444* p) { return p ? p->err.c_str() : g_create_err[0].c_str(); }
+const char* crtfx_unpack444_last_error(const crtfx_unpack444* p) { return p ? p->err.c_str() : create_err<crtfx_unpack444>().c_str(); }
 int crtfx_unpack444_create(int device, int h, int w, int pix_fmt, int layout, const int32_t* m, const int32_t* off, crtfx_unpack444** out_plan) {
-    return create<crtfx_unpack444>(false, device, h, w, pix_fmt, layout, m, off, out_plan);
+    return create(false, device, h, w, pix_fmt, layout, m, off, out_plan);
 }
-int crtfx_unpack444_destroy(crtfx_unpack444* p) { const int rc = destroy(p); delete p; return rc; }
+int crtfx_unpack444_destroy(crtfx_unpack444* p) { return destroy(p); }
 size_t crtfx_unpack444_frame_bytes(const crtfx_unpack444* p) { return p ? p->frame_bytes : 0; }
-int crtfx_unpack444_set_option(crtfx_unpack444* p, int option, int value) { return set_option(p, option, value); }
+int crtfx_unpack444_set_option(crtfx_unpack444* p, int option, int value) { return set_option<Unit>(p, option, value); }
 int crtfx_unpack444_last_plan(crtfx_unpack444* p, char* buf, size_t n) { return last_plan(p, buf, n); }
 int crtfx_unpack444_run(crtfx_unpack444* p, const void* src_base, size_t src_stride_bytes, void* dst_base, size_t dst_stride_bytes, int n, void* stream) {
-    return run(p, src_base, src_stride_bytes, dst_base, dst_stride_bytes, n, stream);
+    return run_frames<Unit>(p, src_base, src_stride_bytes, dst_base, dst_stride_bytes, n, stream);
 }
 
-const char* crtfx_egress444_last_error(const crtfx_egress444* p) { return p ? p->err.c_str() : g_create_err[1].c_str(); }
+const char* crtfx_egress444_last_error(const crtfx_egress444* p) { return p ? p->err.c_str() : create_err<crtfx_egress444>().c_str(); }
 int crtfx_egress444_create(int device, int h, int w, int pix_fmt, int layout, const int32_t* m, const int32_t* off, crtfx_egress444** out_plan) {
-    return create<crtfx_egress444>(true, device, h, w, pix_fmt, layout, m, off, out_plan);
+    return create(true, device, h, w, pix_fmt, layout, m, off, out_plan);
 }
-int crtfx_egress444_destroy(crtfx_egress444* p) { const int rc = destroy(p); delete p; return rc; }
+int crtfx_egress444_destroy(crtfx_egress444* p) { return destroy(p); }
 size_t crtfx_egress444_frame_bytes(const crtfx_egress444* p) { return p ? p->frame_bytes : 0; }
-int crtfx_egress444_set_option(crtfx_egress444* p, int option, int value) { return set_option(p, option, value); }
+int crtfx_egress444_set_option(crtfx_egress444* p, int option, int value) { return set_option<Unit>(p, option, value); }
 int crtfx_egress444_last_plan(crtfx_egress444* p, char* buf, size_t n) { return last_plan(p, buf, n); }
 int crtfx_egress444_run(crtfx_egress444* p, const void* src_base, size_t src_stride_bytes, void* dst_base, size_t dst_stride_bytes, int n, void* stream) {
-    return run(p, src_base, src_stride_bytes, dst_base, dst_stride_bytes, n, stream);
+    return run_frames<Unit>(p, src_base, src_stride_bytes, dst_base, dst_stride_bytes, n, stream);
 }
 
 }  // extern "C"

@@ -1,14 +1,12 @@
 // crtfx_egress.hip — the egress stage of libcrtfx.so (include/crtfx_egress.h): finished uint8 RGB frames -> yuv420p / nv12 on the device.
-// A translation unit of its own: it shares no kernel, table or handle with the effect chain or the ingest stage.
+// A translation unit of its own: it shares no kernel, table or handle with the effect chain or the ingest stage.  The host code around the kernels (checks, frame-group loop, error strings) is
+// the skeleton of crtfx_stage_host.h: host templates only, so nothing is shared at run time either.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdio>
-#include <cstring>
-#include <new>
-#include <string>
 
 #include "crtfx_egress.h"
+#include "crtfx_stage_host.h"
 
 namespace crtfx_egress_impl {
 
@@ -131,145 +129,23 @@ __global__ __launch_bounds__(BLOCK) void k_egress_420_general(Args a) {
 }  // namespace crtfx_egress_impl
 
 using namespace crtfx_egress_impl;
+using namespace crtfx_stage;
 
-struct crtfx_egress {
-    int device = 0;
-    int layout = CRTFX_EGRESS_YUV420P;
-    Args args{};                        // launch constants (frame pointers filled per run)
-    size_t frame_bytes = 0;
-    bool force_general = false;
-    char plan[128] = "";
-    std::string err;
-};
+struct crtfx_egress : StagePlan { Args args{}; };               // `egress` is always true
 
 namespace {
 
-thread_local std::string g_create_err;
-
-int fail(crtfx_egress* p, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (p) p->err = buf; else g_create_err = buf;
-    return code;
-}
-
-struct DeviceGuard {
-    int prev = -1;
-    bool switched = false;
-    hipError_t err = hipSuccess;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) { err = hipSetDevice(dev); switched = err == hipSuccess; }
+struct Unit {
+    static constexpr int block = BLOCK, force_option = CRTFX_EGRESS_OPT_FORCE_GENERAL;
+    static const char* name(bool) { return "egress"; }
+    static void note_plan(crtfx_egress* p, bool vec, int frames) {
+        snprintf(p->plan, sizeof p->plan, "egress=k_egress_420<%s,%s>;frames=%d", p->layout == CRTFX_EGRESS_NV12 ? "nv12" : "yuv420p",
+                 vec ? "vec" : "general", frames);
     }
-    ~DeviceGuard() { if (switched && prev >= 0) (void)hipSetDevice(prev); }
-};
-
-// the accumulator of one row stays in [0, 2^31) for every input: constant + (negative entries) * X >= 0, constant + (positive entries) * X < 2^31
-bool row_fits(const int32_t* row, long long konst, long long x) {
-    long long pos = 0, neg = 0;
-    for (int i = 0; i < 3; ++i) { if (row[i] > 0) pos += row[i]; else neg += row[i]; }
-    return konst + neg * x >= 0 && konst + pos * x < (1LL << 31);
-}
-
-bool vec_fits(const crtfx_egress* p, const void* src, size_t src_stride, const void* dst, size_t dst_stride, int n) {
-    if (p->force_general || (p->args.w & 7)) return false;
-    if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 3u) return false;
-    return n <= 1 || !((src_stride | dst_stride) & 3u);
-}
-
-void note_plan(crtfx_egress* p, bool vec, int frames) {
-    snprintf(p->plan, sizeof p->plan, "egress=k_egress_420<%s,%s>;frames=%d", p->layout == CRTFX_EGRESS_NV12 ? "nv12" : "yuv420p",
-             vec ? "vec" : "general", frames);
-}
-
-}  // namespace
-
-extern "C" {
-
-const char* crtfx_egress_last_error(const crtfx_egress* p) { return p ? p->err.c_str() : g_create_err.c_str(); }
-
-int crtfx_egress_create(int device, int h, int w, int pix_fmt, int layout, const int32_t* m, const int32_t* off, crtfx_egress** out_plan) {
-    g_create_err.clear();
-    if (!out_plan) return fail(nullptr, CRTFX_E_INVALID, "out_plan is null");
-    *out_plan = nullptr;
-    if (pix_fmt == CRTFX_PIX_F16) return fail(nullptr, CRTFX_E_UNSUPPORTED, "only uint8 RGB frames are converted (the egress stage takes finished frames)");
-    if (pix_fmt != CRTFX_PIX_U8) return fail(nullptr, CRTFX_E_INVALID, "unknown pixel format %d", pix_fmt);
-    if (h < 1 || w < 1 || h > 32767 || w > 32767) return fail(nullptr, CRTFX_E_INVALID, "size %dx%d outside 1..32767", h, w);
-    if (layout != CRTFX_EGRESS_YUV420P && layout != CRTFX_EGRESS_NV12) return fail(nullptr, CRTFX_E_INVALID, "unknown layout %d", layout);
-    if (!m || !off) return fail(nullptr, CRTFX_E_INVALID, "a table is null");
-    for (int i = 0; i < 3; ++i)
-        if (off[i] < 0 || off[i] > 255) return fail(nullptr, CRTFX_E_INVALID, "offset %d = %d outside 0..255", i, off[i]);
-    const long long ky = ((long long)off[0] << SH) + (1LL << (SH - 1));
-    const long long ku = ((long long)off[1] << (SH + 2)) + (1LL << (SH + 1)), kv = ((long long)off[2] << (SH + 2)) + (1LL << (SH + 1));
-    if (!row_fits(m, ky, 255) || !row_fits(m + 3, ku, 1020) || !row_fits(m + 6, kv, 1020))
-        return fail(nullptr, CRTFX_E_INVALID, "the matrix lets an accumulator leave [0, 2^31)");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(nullptr, CRTFX_E_HIP, "no HIP device %d", device);
-    DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return fail(nullptr, CRTFX_E_HIP, "hipSetDevice(%d): %s", device, hipGetErrorString(guard.err));
-    crtfx_egress* p = new (std::nothrow) crtfx_egress();
-    if (!p) return fail(nullptr, CRTFX_E_NOMEM, "out of host memory");
-    p->device = device; p->layout = layout;
-    Args& a = p->args;
-    a.h = h; a.w = w; a.ch = (h + 1) / 2; a.cw = (w + 1) / 2;
-    for (int i = 0; i < 9; ++i) a.m[i] = m[i];
-    a.ky = (int)ky; a.ku = (int)ku; a.kv = (int)kv;
-    p->frame_bytes = (size_t)h * w + 2 * (size_t)a.ch * a.cw;
-    note_plan(p, vec_fits(p, nullptr, 0, nullptr, 0, 1), 0);
-    *out_plan = p;
-    return CRTFX_OK;
-}
-
-int crtfx_egress_destroy(crtfx_egress* p) {
-    if (!p) return CRTFX_OK;
-    DeviceGuard guard(p->device);
-    (void)hipDeviceSynchronize();
-    delete p;
-    return CRTFX_OK;
-}
-
-size_t crtfx_egress_frame_bytes(const crtfx_egress* p) { return p ? p->frame_bytes : 0; }
-
-int crtfx_egress_set_option(crtfx_egress* p, int option, int value) {
-    if (!p) return CRTFX_E_INVALID;
-    if (option != CRTFX_EGRESS_OPT_FORCE_GENERAL) return fail(p, CRTFX_E_INVALID, "unknown egress option %d", option);
-    if (value != 0 && value != 1) return fail(p, CRTFX_E_INVALID, "FORCE_GENERAL takes 0 or 1, got %d", value);
-    p->force_general = value != 0;
-    note_plan(p, vec_fits(p, nullptr, 0, nullptr, 0, 1), 0);
-    return CRTFX_OK;
-}
-
-int crtfx_egress_last_plan(crtfx_egress* p, char* buf, size_t n) {
-    if (!p || !buf || n == 0) return CRTFX_E_INVALID;
-    snprintf(buf, n, "%s", p->plan);
-    return CRTFX_OK;
-}
-
-int crtfx_egress_run(crtfx_egress* p, const void* src_base, size_t src_stride_bytes, void* dst_base, size_t dst_stride_bytes, int n, void* stream) {
-    if (!p) return CRTFX_E_INVALID;
-    if (!src_base || !dst_base) return fail(p, CRTFX_E_INVALID, "null frame pointer");
-    if (n < 1) return fail(p, CRTFX_E_INVALID, "n = %d frames", n);
-    const size_t src_bytes = (size_t)p->args.h * p->args.w * 3;
-    if (n > 1 && (src_stride_bytes < src_bytes || dst_stride_bytes < p->frame_bytes))
-        return fail(p, CRTFX_E_INVALID, "frame strides %zu / %zu bytes are smaller than a frame (%zu / %zu)", src_stride_bytes, dst_stride_bytes, src_bytes, p->frame_bytes);
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(p, CRTFX_E_HIP, "hipGetDevice failed");
-    if (dev != p->device) return fail(p, CRTFX_E_INVALID, "current device %d is not the plan's device %d (call hipSetDevice first)", dev, p->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint8_t* src = static_cast<const uint8_t*>(src_base);
-    uint8_t* dst = static_cast<uint8_t*>(dst_base);
-    const bool vec = vec_fits(p, src_base, src_stride_bytes, dst_base, dst_stride_bytes, n);
-    const bool nv12 = p->layout == CRTFX_EGRESS_NV12;
-    const int items = vec ? p->args.ch * (p->args.w >> 3) : p->args.ch * p->args.cw;        // at most 16384 * 16384
-    const int group = 32768;                                                                 // grid.z
-    for (int f = 0; f < n; f += group) {
-        Args a = p->args;
-        a.src = src + (size_t)f * src_stride_bytes; a.src_stride = src_stride_bytes;
-        a.dst = dst + (size_t)f * dst_stride_bytes; a.dst_stride = dst_stride_bytes;
-        const dim3 grid((items + BLOCK - 1) / BLOCK, 1, n - f < group ? n - f : group);
+    static int check_alignment(crtfx_egress*, const void*, size_t, const void*, size_t) { return CRTFX_OK; }    // bytes: any base, any stride
+    static int items(const Args& a, bool vec) { return vec ? a.ch * (a.w >> 3) : a.ch * a.cw; }                // at most 16384 * 16384
+    static void launch(const crtfx_egress* p, bool vec, dim3 grid, hipStream_t st, const Args& a) {
+        const bool nv12 = p->layout == CRTFX_EGRESS_NV12;
         if (vec) {
             if (nv12) hipLaunchKernelGGL(k_egress_420_vec<true>, grid, dim3(BLOCK), 0, st, a);
             else hipLaunchKernelGGL(k_egress_420_vec<false>, grid, dim3(BLOCK), 0, st, a);
@@ -277,11 +153,42 @@ int crtfx_egress_run(crtfx_egress* p, const void* src_base, size_t src_stride_by
             if (nv12) hipLaunchKernelGGL(k_egress_420_general<true>, grid, dim3(BLOCK), 0, st, a);
             else hipLaunchKernelGGL(k_egress_420_general<false>, grid, dim3(BLOCK), 0, st, a);
         }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(p, CRTFX_E_HIP, "egress launch: %s", hipGetErrorString(e));
     }
-    note_plan(p, vec, n);
+};
+
+}  // namespace
+
+extern "C" {
+
+const char* crtfx_egress_last_error(const crtfx_egress* p) { return p ? p->err.c_str() : create_err<crtfx_egress>().c_str(); }
+
+int crtfx_egress_create(int device, int h, int w, int pix_fmt, int layout, const int32_t* m, const int32_t* off, crtfx_egress** out_plan) {
+    using H = crtfx_egress;
+    if (const int rc = begin_create(out_plan)) return rc;
+    if (pix_fmt == CRTFX_PIX_F16) return fail<H>(nullptr, CRTFX_E_UNSUPPORTED, "only uint8 RGB frames are converted (the egress stage takes finished frames)");
+    if (const int rc = check_create<H>(pix_fmt, CRTFX_PIX_U8, h, w, layout, layout == CRTFX_EGRESS_YUV420P || layout == CRTFX_EGRESS_NV12, m, off, 255)) return rc;
+    const long long ky = ((long long)off[0] << SH) + (1LL << (SH - 1));
+    const long long ku = ((long long)off[1] << (SH + 2)) + (1LL << (SH + 1)), kv = ((long long)off[2] << (SH + 2)) + (1LL << (SH + 1));
+    if (!egress_row_fits(m, ky, 255) || !egress_row_fits(m + 3, ku, 1020) || !egress_row_fits(m + 6, kv, 1020))
+        return fail<H>(nullptr, CRTFX_E_INVALID, "the matrix lets an accumulator leave [0, 2^31)");
+    H* p = nullptr;
+    if (const int rc = new_plan(true, device, layout, h, w, m, &p)) return rc;
+    Args& a = p->args;
+    a.ch = (h + 1) / 2; a.cw = (w + 1) / 2;
+    a.ky = (int)ky; a.ku = (int)ku; a.kv = (int)kv;
+    p->frame_bytes = (size_t)h * w + 2 * (size_t)a.ch * a.cw;
+    p->rgb_bytes = (size_t)h * w * 3;
+    Unit::note_plan(p, vec_fits(p, nullptr, 0, nullptr, 0, 1), 0);
+    *out_plan = p;
     return CRTFX_OK;
+}
+
+int crtfx_egress_destroy(crtfx_egress* p) { return destroy(p); }
+size_t crtfx_egress_frame_bytes(const crtfx_egress* p) { return p ? p->frame_bytes : 0; }
+int crtfx_egress_set_option(crtfx_egress* p, int option, int value) { return set_option<Unit>(p, option, value); }
+int crtfx_egress_last_plan(crtfx_egress* p, char* buf, size_t n) { return last_plan(p, buf, n); }
+int crtfx_egress_run(crtfx_egress* p, const void* src_base, size_t src_stride_bytes, void* dst_base, size_t dst_stride_bytes, int n, void* stream) {
+    return run_frames<Unit>(p, src_base, src_stride_bytes, dst_base, dst_stride_bytes, n, stream);
 }
 
 }  // extern "C"

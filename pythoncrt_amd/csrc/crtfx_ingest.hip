@@ -1,15 +1,14 @@
 // crtfx_ingest.hip — the ingest stage of libcrtfx.so (include/crtfx_ingest.h): Pillow's 8-bit BILINEAR resize of uint8 RGB
-// frames on the device.  A translation unit of its own: it shares no kernel, table or handle with the effect chain.
+// frames on the device.  A translation unit of its own: it shares no kernel, table or handle with the effect chain; of the format stages'
+// host skeleton (crtfx_stage_host.h, host templates only) it takes the device guard and the error helper.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <new>
-#include <string>
 #include <vector>
 
 #include "crtfx_ingest.h"
+#include "crtfx_stage_host.h"
 
 namespace crtfx_ingest_impl {
 
@@ -183,6 +182,7 @@ __global__ __launch_bounds__(BLOCK) void k_ingest_v(const uint8_t* tmp, uint8_t*
 }  // namespace crtfx_ingest_impl
 
 using namespace crtfx_ingest_impl;
+using namespace crtfx_stage;       // DeviceGuard, fail and create_err; the plan, create and run are the ingest stage's own
 
 struct crtfx_ingest {
     int device = 0;
@@ -200,29 +200,6 @@ struct crtfx_ingest {
 };
 
 namespace {
-
-thread_local std::string g_create_err;
-
-int fail(crtfx_ingest* p, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (p) p->err = buf; else g_create_err = buf;
-    return code;
-}
-
-struct DeviceGuard {
-    int prev = -1;
-    bool switched = false;
-    hipError_t err = hipSuccess;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) { err = hipSetDevice(dev); switched = err == hipSuccess; }
-    }
-    ~DeviceGuard() { if (switched && prev >= 0) (void)hipSetDevice(prev); }
-};
 
 int log2_ceil(int v) { int s = 0; while ((1 << s) < v) ++s; return s; }
 
@@ -282,28 +259,28 @@ void note_plan(crtfx_ingest* p, int frames) {
 
 extern "C" {
 
-const char* crtfx_ingest_last_error(const crtfx_ingest* p) { return p ? p->err.c_str() : g_create_err.c_str(); }
+const char* crtfx_ingest_last_error(const crtfx_ingest* p) { return p ? p->err.c_str() : create_err<crtfx_ingest>().c_str(); }
 
 int crtfx_ingest_create(int device, int src_h, int src_w, int dst_h, int dst_w, int pix_fmt,
                         const int32_t* x_min, const int32_t* x_count, const int32_t* x_k, int x_ksize,
                         const int32_t* y_min, const int32_t* y_count, const int32_t* y_k, int y_ksize, crtfx_ingest** out_plan) {
-    g_create_err.clear();
-    if (!out_plan) return fail(nullptr, CRTFX_E_INVALID, "out_plan is null");
+    create_err<crtfx_ingest>().clear();
+    if (!out_plan) return fail<crtfx_ingest>(nullptr, CRTFX_E_INVALID, "out_plan is null");
     *out_plan = nullptr;
-    if (pix_fmt == CRTFX_PIX_F16) return fail(nullptr, CRTFX_E_UNSUPPORTED, "only uint8 RGB frames are resized (Pillow has no half image)");
-    if (pix_fmt != CRTFX_PIX_U8) return fail(nullptr, CRTFX_E_INVALID, "unknown pixel format %d", pix_fmt);
+    if (pix_fmt == CRTFX_PIX_F16) return fail<crtfx_ingest>(nullptr, CRTFX_E_UNSUPPORTED, "only uint8 RGB frames are resized (Pillow has no half image)");
+    if (pix_fmt != CRTFX_PIX_U8) return fail<crtfx_ingest>(nullptr, CRTFX_E_INVALID, "unknown pixel format %d", pix_fmt);
     if (src_h < 1 || src_w < 1 || dst_h < 1 || dst_w < 1 || src_h > 32767 || src_w > 32767 || dst_h > 32767 || dst_w > 32767)
-        return fail(nullptr, CRTFX_E_INVALID, "sizes %dx%d -> %dx%d outside 1..32767", src_h, src_w, dst_h, dst_w);
-    if (!x_min || !x_count || !x_k || !y_min || !y_count || !y_k) return fail(nullptr, CRTFX_E_INVALID, "a table is null");
-    if (x_ksize < 1 || y_ksize < 1) return fail(nullptr, CRTFX_E_INVALID, "ksize %d / %d < 1", x_ksize, y_ksize);
-    if (const char* why = check_axis(x_min, x_count, x_k, x_ksize, src_w, dst_w)) return fail(nullptr, CRTFX_E_INVALID, "x tables: %s", why);
-    if (const char* why = check_axis(y_min, y_count, y_k, y_ksize, src_h, dst_h)) return fail(nullptr, CRTFX_E_INVALID, "y tables: %s", why);
+        return fail<crtfx_ingest>(nullptr, CRTFX_E_INVALID, "sizes %dx%d -> %dx%d outside 1..32767", src_h, src_w, dst_h, dst_w);
+    if (!x_min || !x_count || !x_k || !y_min || !y_count || !y_k) return fail<crtfx_ingest>(nullptr, CRTFX_E_INVALID, "a table is null");
+    if (x_ksize < 1 || y_ksize < 1) return fail<crtfx_ingest>(nullptr, CRTFX_E_INVALID, "ksize %d / %d < 1", x_ksize, y_ksize);
+    if (const char* why = check_axis(x_min, x_count, x_k, x_ksize, src_w, dst_w)) return fail<crtfx_ingest>(nullptr, CRTFX_E_INVALID, "x tables: %s", why);
+    if (const char* why = check_axis(y_min, y_count, y_k, y_ksize, src_h, dst_h)) return fail<crtfx_ingest>(nullptr, CRTFX_E_INVALID, "y tables: %s", why);
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(nullptr, CRTFX_E_HIP, "no HIP device %d", device);
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail<crtfx_ingest>(nullptr, CRTFX_E_HIP, "no HIP device %d", device);
     DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return fail(nullptr, CRTFX_E_HIP, "hipSetDevice(%d): %s", device, hipGetErrorString(guard.err));
+    if (guard.err != hipSuccess) return fail<crtfx_ingest>(nullptr, CRTFX_E_HIP, "hipSetDevice(%d): %s", device, hipGetErrorString(guard.err));
     crtfx_ingest* p = new (std::nothrow) crtfx_ingest();
-    if (!p) return fail(nullptr, CRTFX_E_NOMEM, "out of host memory");
+    if (!p) return fail<crtfx_ingest>(nullptr, CRTFX_E_NOMEM, "out of host memory");
     p->device = device; p->sh = src_h; p->sw = src_w; p->dh = dst_h; p->dw = dst_w;
     p->x.ksize = x_ksize; p->y.ksize = y_ksize;
     plan_fused(p, x_min, x_count, y_min, y_count);
@@ -325,7 +302,7 @@ int crtfx_ingest_create(int device, int src_h, int src_w, int dst_h, int dst_w, 
     if (e == hipSuccess) e = hipMemcpy(p->tables, host.data(), host.size() * sizeof(int32_t), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         const int code = e == hipErrorOutOfMemory ? CRTFX_E_NOMEM : CRTFX_E_HIP;
-        fail(nullptr, code, "crtfx_ingest_create: %s", hipGetErrorString(e));
+        fail<crtfx_ingest>(nullptr, code, "crtfx_ingest_create: %s", hipGetErrorString(e));
         if (p->tables) (void)hipFree(p->tables);
         if (p->scratch) (void)hipFree(p->scratch);
         delete p;

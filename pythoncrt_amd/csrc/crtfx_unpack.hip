@@ -1,14 +1,12 @@
 // crtfx_unpack.hip — the source stage of libcrtfx.so (include/crtfx_unpack.h): uint8 yuv420p / nv12 frames -> uint8 RGB on the device.
-// A translation unit of its own: it shares no kernel, table or handle with the effect chain, the ingest stage or the egress stage.
+// A translation unit of its own: it shares no kernel, table or handle with the effect chain, the ingest stage or the egress stage.  The host code around the kernels (checks, frame-group loop, error strings) is
+// the skeleton of crtfx_stage_host.h: host templates only, so nothing is shared at run time either.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdio>
-#include <cstring>
-#include <new>
-#include <string>
 
 #include "crtfx_unpack.h"
+#include "crtfx_stage_host.h"
 
 namespace crtfx_unpack_impl {
 
@@ -132,143 +130,25 @@ __global__ __launch_bounds__(BLOCK) void k_unpack_420_general(Args a) {
 }  // namespace crtfx_unpack_impl
 
 using namespace crtfx_unpack_impl;
+using namespace crtfx_stage;
 
-struct crtfx_unpack {
-    int device = 0;
-    int layout = CRTFX_UNPACK_YUV420P;
-    Args args{};                        // launch constants (frame pointers filled per run)
-    size_t frame_bytes = 0;
-    bool force_general = false;
-    char plan[128] = "";
-    std::string err;
-};
+struct crtfx_unpack : StagePlan { Args args{}; };               // `egress` stays false
 
 namespace {
 
-thread_local std::string g_create_err;
+static_assert(SH == MATRIX_SH, "the row checks of crtfx_stage_host.h assume this matrix scale");
 
-int fail(crtfx_unpack* p, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (p) p->err = buf; else g_create_err = buf;
-    return code;
-}
-
-struct DeviceGuard {
-    int prev = -1;
-    bool switched = false;
-    hipError_t err = hipSuccess;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) { err = hipSetDevice(dev); switched = err == hipSuccess; }
+struct Unit {
+    static constexpr int block = BLOCK, force_option = CRTFX_UNPACK_OPT_FORCE_GENERAL;
+    static const char* name(bool) { return "unpack"; }
+    static void note_plan(crtfx_unpack* p, bool vec, int frames) {
+        snprintf(p->plan, sizeof p->plan, "unpack=k_unpack_420<%s,%s>;frames=%d", p->layout == CRTFX_UNPACK_NV12 ? "nv12" : "yuv420p",
+                 vec ? "vec" : "general", frames);
     }
-    ~DeviceGuard() { if (switched && prev >= 0) (void)hipSetDevice(prev); }
-};
-
-// the accumulator of one row stays inside int32 for every input: |c|, |d|, |e| <= 255
-bool row_fits(const int32_t* row) {
-    long long s = 1LL << (SH - 1);
-    for (int i = 0; i < 3; ++i) s += (row[i] < 0 ? -(long long)row[i] : (long long)row[i]) * 255;
-    return s < (1LL << 31);
-}
-
-bool vec_fits(const crtfx_unpack* p, const void* src, size_t src_stride, const void* dst, size_t dst_stride, int n) {
-    if (p->force_general || (p->args.w & 7)) return false;
-    if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 3u) return false;
-    return n <= 1 || !((src_stride | dst_stride) & 3u);
-}
-
-void note_plan(crtfx_unpack* p, bool vec, int frames) {
-    snprintf(p->plan, sizeof p->plan, "unpack=k_unpack_420<%s,%s>;frames=%d", p->layout == CRTFX_UNPACK_NV12 ? "nv12" : "yuv420p",
-             vec ? "vec" : "general", frames);
-}
-
-}  // namespace
-
-extern "C" {
-
-const char* crtfx_unpack_last_error(const crtfx_unpack* p) { return p ? p->err.c_str() : g_create_err.c_str(); }
-
-int crtfx_unpack_create(int device, int h, int w, int pix_fmt, int layout, const int32_t* m, const int32_t* off, crtfx_unpack** out_plan) {
-    g_create_err.clear();
-    if (!out_plan) return fail(nullptr, CRTFX_E_INVALID, "out_plan is null");
-    *out_plan = nullptr;
-    if (pix_fmt == CRTFX_PIX_F16) return fail(nullptr, CRTFX_E_UNSUPPORTED, "only uint8 RGB frames are written (the source stage feeds the chain's uint8 input)");
-    if (pix_fmt != CRTFX_PIX_U8) return fail(nullptr, CRTFX_E_INVALID, "unknown pixel format %d", pix_fmt);
-    if (h < 1 || w < 1 || h > 32767 || w > 32767) return fail(nullptr, CRTFX_E_INVALID, "size %dx%d outside 1..32767", h, w);
-    if (layout != CRTFX_UNPACK_YUV420P && layout != CRTFX_UNPACK_NV12) return fail(nullptr, CRTFX_E_INVALID, "unknown layout %d", layout);
-    if (!m || !off) return fail(nullptr, CRTFX_E_INVALID, "a table is null");
-    for (int i = 0; i < 3; ++i)
-        if (off[i] < 0 || off[i] > 255) return fail(nullptr, CRTFX_E_INVALID, "offset %d = %d outside 0..255", i, off[i]);
-    if (!row_fits(m) || !row_fits(m + 3) || !row_fits(m + 6))
-        return fail(nullptr, CRTFX_E_INVALID, "the matrix lets an accumulator leave int32");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(nullptr, CRTFX_E_HIP, "no HIP device %d", device);
-    DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return fail(nullptr, CRTFX_E_HIP, "hipSetDevice(%d): %s", device, hipGetErrorString(guard.err));
-    crtfx_unpack* p = new (std::nothrow) crtfx_unpack();
-    if (!p) return fail(nullptr, CRTFX_E_NOMEM, "out of host memory");
-    p->device = device; p->layout = layout;
-    Args& a = p->args;
-    a.h = h; a.w = w; a.ch = (h + 1) / 2; a.cw = (w + 1) / 2;
-    for (int i = 0; i < 9; ++i) a.m[i] = m[i];
-    for (int i = 0; i < 3; ++i) a.off[i] = off[i];
-    p->frame_bytes = (size_t)h * w + 2 * (size_t)a.ch * a.cw;
-    note_plan(p, vec_fits(p, nullptr, 0, nullptr, 0, 1), 0);
-    *out_plan = p;
-    return CRTFX_OK;
-}
-
-int crtfx_unpack_destroy(crtfx_unpack* p) {
-    if (!p) return CRTFX_OK;
-    DeviceGuard guard(p->device);
-    (void)hipDeviceSynchronize();
-    delete p;
-    return CRTFX_OK;
-}
-
-size_t crtfx_unpack_frame_bytes(const crtfx_unpack* p) { return p ? p->frame_bytes : 0; }
-
-int crtfx_unpack_set_option(crtfx_unpack* p, int option, int value) {
-    if (!p) return CRTFX_E_INVALID;
-    if (option != CRTFX_UNPACK_OPT_FORCE_GENERAL) return fail(p, CRTFX_E_INVALID, "unknown unpack option %d", option);
-    if (value != 0 && value != 1) return fail(p, CRTFX_E_INVALID, "FORCE_GENERAL takes 0 or 1, got %d", value);
-    p->force_general = value != 0;
-    note_plan(p, vec_fits(p, nullptr, 0, nullptr, 0, 1), 0);
-    return CRTFX_OK;
-}
-
-int crtfx_unpack_last_plan(crtfx_unpack* p, char* buf, size_t n) {
-    if (!p || !buf || n == 0) return CRTFX_E_INVALID;
-    snprintf(buf, n, "%s", p->plan);
-    return CRTFX_OK;
-}
-
-int crtfx_unpack_run(crtfx_unpack* p, const void* src_base, size_t src_stride_bytes, void* dst_base, size_t dst_stride_bytes, int n, void* stream) {
-    if (!p) return CRTFX_E_INVALID;
-    if (!src_base || !dst_base) return fail(p, CRTFX_E_INVALID, "null frame pointer");
-    if (n < 1) return fail(p, CRTFX_E_INVALID, "n = %d frames", n);
-    const size_t dst_bytes = (size_t)p->args.h * p->args.w * 3;
-    if (n > 1 && (src_stride_bytes < p->frame_bytes || dst_stride_bytes < dst_bytes))
-        return fail(p, CRTFX_E_INVALID, "frame strides %zu / %zu bytes are smaller than a frame (%zu / %zu)", src_stride_bytes, dst_stride_bytes, p->frame_bytes, dst_bytes);
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(p, CRTFX_E_HIP, "hipGetDevice failed");
-    if (dev != p->device) return fail(p, CRTFX_E_INVALID, "current device %d is not the plan's device %d (call hipSetDevice first)", dev, p->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint8_t* src = static_cast<const uint8_t*>(src_base);
-    uint8_t* dst = static_cast<uint8_t*>(dst_base);
-    const bool vec = vec_fits(p, src_base, src_stride_bytes, dst_base, dst_stride_bytes, n);
-    const bool nv12 = p->layout == CRTFX_UNPACK_NV12;
-    const int items = vec ? p->args.ch * (p->args.w >> 3) : p->args.ch * p->args.cw;        // at most 16384 * 16384
-    const int group = 32768;                                                                 // grid.z
-    for (int f = 0; f < n; f += group) {
-        Args a = p->args;
-        a.src = src + (size_t)f * src_stride_bytes; a.src_stride = src_stride_bytes;
-        a.dst = dst + (size_t)f * dst_stride_bytes; a.dst_stride = dst_stride_bytes;
-        const dim3 grid((items + BLOCK - 1) / BLOCK, 1, n - f < group ? n - f : group);
+    static int check_alignment(crtfx_unpack*, const void*, size_t, const void*, size_t) { return CRTFX_OK; }    // bytes: any base, any stride
+    static int items(const Args& a, bool vec) { return vec ? a.ch * (a.w >> 3) : a.ch * a.cw; }                // at most 16384 * 16384
+    static void launch(const crtfx_unpack* p, bool vec, dim3 grid, hipStream_t st, const Args& a) {
+        const bool nv12 = p->layout == CRTFX_UNPACK_NV12;
         if (vec) {
             if (nv12) hipLaunchKernelGGL(k_unpack_420_vec<true>, grid, dim3(BLOCK), 0, st, a);
             else hipLaunchKernelGGL(k_unpack_420_vec<false>, grid, dim3(BLOCK), 0, st, a);
@@ -276,11 +156,40 @@ int crtfx_unpack_run(crtfx_unpack* p, const void* src_base, size_t src_stride_by
             if (nv12) hipLaunchKernelGGL(k_unpack_420_general<true>, grid, dim3(BLOCK), 0, st, a);
             else hipLaunchKernelGGL(k_unpack_420_general<false>, grid, dim3(BLOCK), 0, st, a);
         }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(p, CRTFX_E_HIP, "unpack launch: %s", hipGetErrorString(e));
     }
-    note_plan(p, vec, n);
+};
+
+}  // namespace
+
+extern "C" {
+
+const char* crtfx_unpack_last_error(const crtfx_unpack* p) { return p ? p->err.c_str() : create_err<crtfx_unpack>().c_str(); }
+
+int crtfx_unpack_create(int device, int h, int w, int pix_fmt, int layout, const int32_t* m, const int32_t* off, crtfx_unpack** out_plan) {
+    using H = crtfx_unpack;
+    if (const int rc = begin_create(out_plan)) return rc;
+    if (pix_fmt == CRTFX_PIX_F16) return fail<H>(nullptr, CRTFX_E_UNSUPPORTED, "only uint8 RGB frames are written (the source stage feeds the chain's uint8 input)");
+    if (const int rc = check_create<H>(pix_fmt, CRTFX_PIX_U8, h, w, layout, layout == CRTFX_UNPACK_YUV420P || layout == CRTFX_UNPACK_NV12, m, off, 255)) return rc;
+    if (!source_row_fits(m, 255) || !source_row_fits(m + 3, 255) || !source_row_fits(m + 6, 255))
+        return fail<H>(nullptr, CRTFX_E_INVALID, "the matrix lets an accumulator leave int32");
+    H* p = nullptr;
+    if (const int rc = new_plan(false, device, layout, h, w, m, &p)) return rc;
+    Args& a = p->args;
+    a.ch = (h + 1) / 2; a.cw = (w + 1) / 2;
+    for (int i = 0; i < 3; ++i) a.off[i] = off[i];
+    p->frame_bytes = (size_t)h * w + 2 * (size_t)a.ch * a.cw;
+    p->rgb_bytes = (size_t)h * w * 3;
+    Unit::note_plan(p, vec_fits(p, nullptr, 0, nullptr, 0, 1), 0);
+    *out_plan = p;
     return CRTFX_OK;
+}
+
+int crtfx_unpack_destroy(crtfx_unpack* p) { return destroy(p); }
+size_t crtfx_unpack_frame_bytes(const crtfx_unpack* p) { return p ? p->frame_bytes : 0; }
+int crtfx_unpack_set_option(crtfx_unpack* p, int option, int value) { return set_option<Unit>(p, option, value); }
+int crtfx_unpack_last_plan(crtfx_unpack* p, char* buf, size_t n) { return last_plan(p, buf, n); }
+int crtfx_unpack_run(crtfx_unpack* p, const void* src_base, size_t src_stride_bytes, void* dst_base, size_t dst_stride_bytes, int n, void* stream) {
+    return run_frames<Unit>(p, src_base, src_stride_bytes, dst_base, dst_stride_bytes, n, stream);
 }
 
 }  // extern "C"

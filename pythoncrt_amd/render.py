@@ -20,21 +20,17 @@ from typing import Callable, Iterable, Optional, Tuple
 
 import numpy as np
 
+from . import formats
+
 # process_video keywords that belong to its container / codec plumbing (out of scope): accepted so that a caller can forward its
 # own keyword dictionary unchanged, and ignored
-_DEEP_FMTS = ("yuv420p10le", "p010le")          # the 10-bit 4:2:0 formats: both ends or neither (process_frames)
-_DEEP444_FMTS = ("yuv444p10le", "gbrp10le", "x2rgb10le")   # the 10-bit 4:4:4 formats: members of the 10-bit family, any pairing with it
-_422_FMTS = ("yuv422p", "yuyv422", "uyvy422")   # the 8-bit 4:2:2 formats: members of the 8-bit family, either end
 _IO_KEYS = ("input_path", "output_path", "width", "height", "fps", "crf", "target_bitrate_kbps", "gpu", "nvenc_preset", "encoder_preference",
             "decoder_preference")
 
 
-def iter_rgb24(stream, out_w: int, out_h: int):
-    """The frame iterator of the reference's FFmpegRawReader.iter_frames (ref:495-506) over an ALREADY OPEN byte stream of raw rgb24 — the
-    stdout of an ffmpeg process the caller started (`-f rawvideo -pix_fmt rgb24 -`), a file, a pipe: frames of out_h x out_w x 3 uint8 until the
-    stream ends; a trailing partial frame is dropped, as there.  (The reader class itself — spawning ffmpeg, hw-accel flags — is codec plumbing
-    and stays the reference's.)"""
-    frame_size = int(out_w) * int(out_h) * 3
+def _iter_frames(stream, frame_size: int):
+    """Whole frames of frame_size bytes from an already open byte stream, as 1-D uint8 arrays, until the stream ends; a trailing partial
+    frame is dropped."""
     while True:
         buf = stream.read(frame_size)
         while buf and len(buf) < frame_size:           # a pipe may return less than asked for: keep reading until the frame is whole or the stream ends
@@ -44,7 +40,16 @@ def iter_rgb24(stream, out_w: int, out_h: int):
             buf += more
         if not buf or len(buf) < frame_size:
             return
-        yield np.frombuffer(buf, dtype=np.uint8).reshape((int(out_h), int(out_w), 3))
+        yield np.frombuffer(buf, dtype=np.uint8)
+
+
+def iter_rgb24(stream, out_w: int, out_h: int):
+    """The frame iterator of the reference's FFmpegRawReader.iter_frames (ref:495-506) over an ALREADY OPEN byte stream of raw rgb24 — the
+    stdout of an ffmpeg process the caller started (`-f rawvideo -pix_fmt rgb24 -`), a file, a pipe: frames of out_h x out_w x 3 uint8 until the
+    stream ends; a trailing partial frame is dropped, as there.  (The reader class itself — spawning ffmpeg, hw-accel flags — is codec plumbing
+    and stays the reference's.)"""
+    for frame in _iter_frames(stream, formats.frame_bytes(out_h, out_w, "rgb24")):
+        yield frame.reshape((int(out_h), int(out_w), 3))
 
 
 def iter_yuv420(stream, w: int, h: int, bits: int = 8):
@@ -53,56 +58,23 @@ def iter_yuv420(stream, w: int, h: int, bits: int = 8):
     ends; the same short-read handling, a trailing partial frame is dropped.  Both layouts have the same size: the bytes are not interpreted here.
     `bits=10` reads yuv420p10le / p010le (`-pix_fmt yuv420p10le -` / `-pix_fmt p010le -`): the same, with frames of twice as many bytes
     (16-bit little-endian words), still handed out as 1-D uint8 arrays."""
-    from .egress import frame_bytes
     if bits not in (8, 10):
         raise ValueError(f"bits must be 8 or 10, got {bits!r}")
-    frame_size = frame_bytes(int(h), int(w)) * (2 if bits == 10 else 1)
-    while True:
-        buf = stream.read(frame_size)
-        while buf and len(buf) < frame_size:           # a pipe may return less than asked for: keep reading until the frame is whole or the stream ends
-            more = stream.read(frame_size - len(buf))
-            if not more:
-                break
-            buf += more
-        if not buf or len(buf) < frame_size:
-            return
-        yield np.frombuffer(buf, dtype=np.uint8)
+    return _iter_frames(stream, formats.frame_bytes(h, w, "yuv420p10le" if bits == 10 else "yuv420p"))
 
 
 def iter_yuv422(stream, w: int, h: int, layout: str):
     """`iter_yuv420` for an already open byte stream of raw yuv422p, yuyv422 or uyvy422 (`-f rawvideo -pix_fmt uyvy422 -`): 1-D uint8 arrays of
     yuv422.frame_bytes(h, w, layout) bytes — what `process_frames(..., in_pix_fmt=layout)` takes — until the stream ends; the same
     short-read handling, a trailing partial frame is dropped.  The bytes are not interpreted here."""
-    from .yuv422 import frame_bytes
-    frame_size = frame_bytes(int(h), int(w), layout)
-    while True:
-        buf = stream.read(frame_size)
-        while buf and len(buf) < frame_size:           # a pipe may return less than asked for: keep reading until the frame is whole or the stream ends
-            more = stream.read(frame_size - len(buf))
-            if not more:
-                break
-            buf += more
-        if not buf or len(buf) < frame_size:
-            return
-        yield np.frombuffer(buf, dtype=np.uint8)
+    return _iter_frames(stream, formats.YUV422.frame_bytes(int(h), int(w), layout))
 
 
 def iter_deep444(stream, w: int, h: int, fmt: str):
     """`iter_yuv422` for an already open byte stream of raw yuv444p10le, gbrp10le or x2rgb10le (`-f rawvideo -pix_fmt gbrp10le -`): 1-D uint8
     arrays of deep444.frame_bytes(h, w, fmt) bytes — what `process_frames(..., in_pix_fmt=fmt)` takes — until the stream ends; the same
     short-read handling, a trailing partial frame is dropped.  The bytes are not interpreted here."""
-    from .deep444 import frame_bytes
-    frame_size = frame_bytes(int(h), int(w), fmt)
-    while True:
-        buf = stream.read(frame_size)
-        while buf and len(buf) < frame_size:           # a pipe may return less than asked for: keep reading until the frame is whole or the stream ends
-            more = stream.read(frame_size - len(buf))
-            if not more:
-                break
-            buf += more
-        if not buf or len(buf) < frame_size:
-            return
-        yield np.frombuffer(buf, dtype=np.uint8)
+    return _iter_frames(stream, formats.DEEP444.frame_bytes(int(h), int(w), fmt))
 
 
 def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.ndarray], None], out_w: int, out_h: int, fps_out: float,
@@ -167,14 +139,14 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         raise TypeError(f"process_frames() got unexpected keyword arguments {sorted(unknown)}")
     if resize_on not in ("device", "host"):
         raise ValueError(f"resize_on must be 'device' or 'host', got {resize_on!r}")
-    if out_pix_fmt not in ("rgb24", "yuv420p", "nv12") + _422_FMTS + _DEEP_FMTS + _DEEP444_FMTS:
+    if out_pix_fmt not in formats.PIX_FMTS:
         raise ValueError("out_pix_fmt must be 'rgb24', 'yuv420p' or 'nv12', 'yuv422p', 'yuyv422' or 'uyvy422' (or, with a 10-bit input, "
                          f"'yuv420p10le' or 'p010le', 'yuv444p10le', 'gbrp10le' or 'x2rgb10le'), got {out_pix_fmt!r}")
-    if in_pix_fmt not in ("rgb24", "yuv420p", "nv12") + _422_FMTS + _DEEP_FMTS + _DEEP444_FMTS:
+    if in_pix_fmt not in formats.PIX_FMTS:
         raise ValueError("in_pix_fmt must be 'rgb24', 'yuv420p' or 'nv12', 'yuv422p', 'yuyv422' or 'uyvy422' (or, with a 10-bit output, "
                          f"'yuv420p10le' or 'p010le', 'yuv444p10le', 'gbrp10le' or 'x2rgb10le'), got {in_pix_fmt!r}")
-    deep = in_pix_fmt in _DEEP_FMTS + _DEEP444_FMTS
-    if deep != (out_pix_fmt in _DEEP_FMTS + _DEEP444_FMTS):
+    deep = formats.bits(in_pix_fmt) == 10                                      # both ends or neither
+    if deep != (formats.bits(out_pix_fmt) == 10):
         raise ValueError(f"in_pix_fmt={in_pix_fmt!r} with out_pix_fmt={out_pix_fmt!r}: a 10-bit format on one end only — the chain between "
                          "them runs on half pixels or on uint8 ones, and the 8-bit stages have no half path (the 10-bit ones no uint8 path)")
     if deep and in_size is not None and (int(in_size[0]), int(in_size[1])) != (int(out_h), int(out_w)):
@@ -211,15 +183,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
               for _ in range(NS)]
     egress = None
     if out_pix_fmt != "rgb24":                                                 # the encoder's format: converted on the device, half the bytes downloaded
-        if out_pix_fmt in _DEEP444_FMTS:
-            from .deep444 import EgressDeep444 as EgressYuv
-        elif deep:
-            from .deep import EgressYuv10 as EgressYuv
-        elif out_pix_fmt in _422_FMTS:
-            from .yuv422 import EgressYuv422 as EgressYuv
-        else:
-            from .egress import EgressYuv
-        egress = EgressYuv(dev, (h, w), layout=out_pix_fmt, matrix=out_matrix, range=out_range)
+        egress = formats.FORMATS[out_pix_fmt].egress(dev, (h, w), layout=out_pix_fmt, matrix=out_matrix, range=out_range)
     out_shape = (B, h, w, 3) if egress is None else (B, egress.frame_bytes)    # what is downloaded and handed to the writer
     pin_out = [torch.empty(out_shape, dtype=torch.uint8).pin_memory() for _ in range(NS)]
     dev_in = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]
@@ -255,28 +219,13 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
 
     YUV = "yuv"                      # the key of the one 4:2:0 / 4:2:2 source (its size is fixed by in_size)
     yuv_hw = (h, w) if in_size is None else (int(in_size[0]), int(in_size[1]))
-    if in_pix_fmt in _422_FMTS:
-        from .yuv422 import frame_bytes as _bytes422
-        yuv_bytes = _bytes422(yuv_hw[0], yuv_hw[1], in_pix_fmt)
-    elif in_pix_fmt in _DEEP444_FMTS:
-        from .deep444 import frame_bytes as _bytes444
-        yuv_bytes = _bytes444(yuv_hw[0], yuv_hw[1], in_pix_fmt)
-    else:
-        yuv_bytes = (yuv_hw[0] * yuv_hw[1] + 2 * ((yuv_hw[0] + 1) // 2) * ((yuv_hw[1] + 1) // 2)) * (2 if deep else 1)
+    yuv_bytes = formats.frame_bytes(yuv_hw[0], yuv_hw[1], in_pix_fmt)
 
     class _YuvSource:
         """Staging of a 4:2:0 or 4:2:2 input: pinned and device slots of frame_bytes(*in_size) bytes per frame, the plan that converts them to RGB —
         into dev_in[d] itself, or, where in_size is not the output size, into RGB slots of that size which IngestResize brings to dev_in[d]."""
         def __init__(self):
-            if in_pix_fmt in _DEEP444_FMTS:
-                from .deep444 import UnpackDeep444 as UnpackYuv
-            elif deep:
-                from .deep import UnpackYuv10 as UnpackYuv
-            elif in_pix_fmt in _422_FMTS:
-                from .yuv422 import UnpackYuv422 as UnpackYuv
-            else:
-                from .unpack import UnpackYuv
-            self.plan = UnpackYuv(dev, yuv_hw, layout=in_pix_fmt, matrix=in_matrix, range=in_range)
+            self.plan = formats.FORMATS[in_pix_fmt].source(dev, yuv_hw, layout=in_pix_fmt, matrix=in_matrix, range=in_range)
             self.nbytes = self.plan.frame_bytes
             assert self.nbytes == yuv_bytes
             self.resize, self.rgb = None, None

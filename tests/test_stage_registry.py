@@ -1,0 +1,85 @@
+"""The one format registry (pythoncrt_amd/formats.py) against the CLI's flags and the family modules, and the generated ctypes tables of the
+format stages (_lib.stage_symbols) against the seven entry points written out.  No GPU."""
+import argparse
+import ctypes
+
+import pytest
+
+from pythoncrt_amd import _lib, cli, deep, deep444, egress, formats, unpack, yuv422
+
+SIZES = [(1, 1), (2, 8), (3, 5), (1080, 1920)]
+
+
+def _choices(add_flags, flag):
+    parser = add_flags(argparse.ArgumentParser())
+    return next(a.choices for a in parser._actions if flag in a.option_strings)
+
+
+def test_the_cli_accepts_exactly_the_registry():
+    """Every name --in-pix-fmt / --out-pix-fmt accept is a registry entry (or rgb24, the chain's own format, which needs no stage), and
+    every registry entry is accepted on both ends; process_frames takes the same names."""
+    for got in (_choices(cli.add_input_flags, "--in-pix-fmt"), _choices(cli.add_output_flags, "--out-pix-fmt"), cli.IN_PIX_FMTS, cli.OUT_PIX_FMTS):
+        assert len(got) == len(set(got)) and set(got) - {"rgb24"} == set(formats.FORMATS) and "rgb24" in got, got
+    assert "rgb24" not in formats.FORMATS and formats.PIX_FMTS == ("rgb24",) + tuple(formats.FORMATS)
+    assert set(formats.FORMATS) == {"yuv420p", "nv12", "yuv422p", "yuyv422", "uyvy422", "yuv420p10le", "p010le", "yuv444p10le", "gbrp10le", "x2rgb10le"}
+    assert cli.DEEP_PIX_FMTS + cli.DEEP444_PIX_FMTS == tuple(f for f in formats.FORMATS if formats.bits(f) == 10)
+    assert formats.bits("rgb24") == 8 and all(formats.bits(f) == 8 for f in ("yuv420p", "nv12") + cli.YUV422_PIX_FMTS)
+
+
+def test_every_format_names_its_family():
+    """The classes and the sample depth of each entry: the source and egress plan of the family module that lists the format."""
+    modules = {unpack: (unpack.UnpackYuv, egress.EgressYuv, egress.LAYOUTS, 8), yuv422: (yuv422.UnpackYuv422, yuv422.EgressYuv422, yuv422.LAYOUTS, 8),
+               deep: (deep.UnpackYuv10, deep.EgressYuv10, deep.LAYOUTS, 10), deep444: (deep444.UnpackDeep444, deep444.EgressDeep444, deep444.FORMATS, 10)}
+    seen = []
+    for source, sink, names, bits in modules.values():
+        for name in names:
+            fam = formats.FORMATS[name]
+            assert (fam.source, fam.egress, fam.bits) == (source, sink, bits) and name in fam.names, name
+            assert name in source._layouts and name in sink._layouts
+            seen.append(name)
+    assert sorted(seen) == sorted(formats.FORMATS)
+
+
+@pytest.mark.parametrize("size", SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_frame_bytes_are_the_family_modules(size):
+    h, w = size
+    for fmt in ("yuv420p", "nv12"):
+        assert formats.frame_bytes(h, w, fmt) == egress.frame_bytes(h, w) == unpack.frame_bytes(h, w) == formats.FORMATS[fmt].frame_bytes(h, w, fmt)
+    for fmt in yuv422.LAYOUTS:
+        assert formats.frame_bytes(h, w, fmt) == yuv422.frame_bytes(h, w, fmt) == formats.FORMATS[fmt].frame_bytes(h, w, fmt)
+    for fmt in deep.LAYOUTS:
+        assert formats.frame_bytes(h, w, fmt) == deep.frame_bytes(h, w) == formats.FORMATS[fmt].frame_bytes(h, w, fmt)
+    for fmt in deep444.FORMATS:
+        assert formats.frame_bytes(h, w, fmt) == deep444.frame_bytes(h, w, fmt) == formats.FORMATS[fmt].frame_bytes(h, w, fmt)
+    assert formats.frame_bytes(h, w, "rgb24") == h * w * 3
+    ch, cw = (h + 1) // 2, (w + 1) // 2                                        # ... and the sizes themselves, written out
+    assert formats.frame_bytes(h, w, "nv12") == h * w + 2 * ch * cw and formats.frame_bytes(h, w, "p010le") == 2 * (h * w + 2 * ch * cw)
+    assert formats.frame_bytes(h, w, "yuv422p") == h * w + 2 * h * cw and formats.frame_bytes(h, w, "uyvy422") == 4 * h * cw
+    assert formats.frame_bytes(h, w, "gbrp10le") == 6 * h * w and formats.frame_bytes(h, w, "x2rgb10le") == 4 * h * w
+
+
+def _literal(fam):
+    vp = ctypes.c_void_p
+    return {
+        f"crtfx_{fam}_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.POINTER(vp)]),
+        f"crtfx_{fam}_destroy": (ctypes.c_int, [vp]),
+        f"crtfx_{fam}_last_error": (ctypes.c_char_p, [vp]),
+        f"crtfx_{fam}_frame_bytes": (ctypes.c_size_t, [vp]),
+        f"crtfx_{fam}_run": (ctypes.c_int, [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_int, vp]),
+        f"crtfx_{fam}_set_option": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
+        f"crtfx_{fam}_last_plan": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t]),
+    }
+
+
+@pytest.mark.parametrize("table,families", [("EGRESS_SYMBOLS", ("egress",)), ("UNPACK_SYMBOLS", ("unpack",)), ("DEEP_SYMBOLS", ("unpack10", "egress10")),
+                                            ("YUV422_SYMBOLS", ("unpack422", "egress422")), ("DEEP444_SYMBOLS", ("unpack444", "egress444"))])
+def test_generated_symbol_tables_equal_the_literal_seven(table, families):
+    want = {}
+    for fam in families:
+        want.update(_literal(fam))
+    got = getattr(_lib, table)
+    assert got == want and len(got) == 7 * len(families) and list(got) == list(want)
+    assert got == _lib.stage_symbols(*families)
+    for fam in families:                                                       # the classes call exactly these families
+        users = [c for f in formats.FORMATS.values() for c in (f.source, f.egress) if c._family == fam]
+        assert users, fam
