@@ -84,14 +84,33 @@ class VignetteMask:
 # The verdict is remembered per array OBJECT: the entry keeps a reference to the array (so its id cannot be reused by
 # another array while the entry lives) together with a fingerprint of a strided sample (an in-place rebuild of the
 # mask is then looked at again).  At most four arrays are held.
+# What the sample sees of an array RECOGNISED as reference-built: a rebuild in place (another strength or softness, any
+# change that reaches the sampled rows and columns) — the array is verified again.  What it does not see: an edit of
+# single elements off the sampled rows / columns; such an array keeps its descriptor until its object is replaced.  That
+# is the price of not reading 99.5 MB + 66 MB per call at 4K.  An array that is NOT recognised (a per-pixel plane) is
+# compared, all of it, with the host copy kept from its upload (Engine.set_params / _plane_changed): every in-place change is seen.
 _RECOGNISED = {}      # (kind, id(array)) -> (array, fingerprint, descriptor or False)
 _RECOGNISED_MAX = 4
 _RECOGNISED_LOCK = threading.Lock()     # apply_static_effects is called from the reference's two worker threads
 
 
 def _fingerprint(a: np.ndarray) -> int:
+    """A strided sample of a mask array: rows ::h//8, columns ::w//64 (every channel of those).  Sees a rebuild of a
+    reference-built mask; does not see single elements off those rows / columns."""
     step = max(1, a.shape[0] // 8)
     return hash((a.shape, a[::step, :: max(1, a.shape[1] // 64)].tobytes()))
+
+
+def _plane_bits(a: np.ndarray) -> np.ndarray:
+    a = np.ascontiguousarray(a).reshape(-1)
+    return a.view({4: np.uint32, 8: np.uint64}.get(a.dtype.itemsize, np.uint8))
+
+
+def _plane_changed(kept: Optional[np.ndarray], a: np.ndarray) -> bool:
+    """A per-pixel plane handed in as a plain array against the host copy kept from the call that uploaded it: True when any bit of
+    it differs.  The reference reads the array on every call, so any in-place change must reach the device.  One pass over both
+    arrays per call (profiles/mask_key_cost.txt); the path uploads H x W x 3 floats per change anyway."""
+    return kept is None or kept.shape != a.shape or kept.dtype != a.dtype or not np.array_equal(_plane_bits(kept), _plane_bits(a))
 
 
 def _lookup(kind, mask):
@@ -305,7 +324,8 @@ class Engine:
     # -- params ------------------------------------------------------------------------
     def set_params(self, s: "Settings"):
         key = s.key()
-        if key == self.params_key:
+        planes = s.planes()
+        if key == self.params_key and not any(_plane_changed(self.keep.get("host_" + f), a) for f, a in planes.items()):
             return
         h, w = self.h, self.w
         p = _lib.CrtfxParams()
@@ -406,6 +426,8 @@ class Engine:
         p.flags = flags
         with torch.cuda.device(self.device):
             _lib.check(self.lib, self.ctx, self.lib.crtfx_set_params(self.ctx, ctypes.byref(p)))
+        for f, a in planes.items():            # what the device now holds, to compare the caller's array with on the next call
+            keep["host_" + f] = np.array(a, copy=True)
         self.keep = keep
         self.flags = flags
         self.params_key = key
@@ -520,16 +542,22 @@ class Settings:
         for f in self.FIELDS:
             v = getattr(self, f)
             if f in ("triad_mask", "vignette_mask") and v is not None:
-                # a plain array / tensor mask is a per-pixel plane: keyed by identity AND a strided-sample fingerprint (or
-                # the tensor's version counter), so a mask rebuilt in place — or an id reused after a free — is uploaded again
+                # a plain array / tensor mask is a per-pixel plane: a tensor is keyed by identity and its version counter, an array
+                # by identity and shape — and compared, all of it, with the host copy of the last upload (planes(); Engine.set_params) —
+                # so a mask changed in place anywhere, or an id reused after a free, is uploaded again
                 if hasattr(v, "key"):
                     v = v.key()
                 elif isinstance(v, torch.Tensor):
                     v = ("tensor", id(v), v.data_ptr(), tuple(v.shape), v._version)
                 else:
-                    v = ("array", id(v), _fingerprint(np.asarray(v)) if np.asarray(v).ndim >= 2 else hash(np.asarray(v).tobytes()))
+                    v = ("array", id(v), np.asarray(v).shape, np.asarray(v).dtype.str)
             out.append(v)
         return tuple(out)
+
+    def planes(self):
+        """{field: array} of the masks handed in as plain numpy-like arrays (per-pixel planes whose content key() does not cover)."""
+        return {f: np.asarray(getattr(self, f)) for f in ("triad_mask", "vignette_mask")
+                if getattr(self, f) is not None and not hasattr(getattr(self, f), "key") and not isinstance(getattr(self, f), torch.Tensor)}
 
 
 def _frame_to_device(frame):

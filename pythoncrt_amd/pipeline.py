@@ -110,7 +110,7 @@ class FramePipeline:
 
     def __init__(self, device: torch.device, h: int, w: int, settings: RenderSettings, fps: float = 30.0,
                  noise_seed: int = 0, dtype: torch.dtype = torch.uint8, text_overlay_rgba=None, text_overlay_after: bool = True):
-        self.device, self.h, self.w, self.rs, self.fps = device, int(h), int(w), settings, float(fps)
+        self.device, self.h, self.w, self.fps = device, int(h), int(w), float(fps)
         # the one overlay plane of a render (ref:1076-1077: built once per frame there, identical every time)
         self.overlay = _overlay_tensor(text_overlay_rgba, device, int(h), int(w)) if text_overlay_rgba is not None else None
         self.overlay_after = bool(text_overlay_after)
@@ -118,10 +118,16 @@ class FramePipeline:
         self.dtype = dtype                  # torch.uint8, or torch.float16 (half frames on the 0..255 scale)
         self._glitch_stage = {}             # (frames, rows, segments) -> {"slots": two [pinned int32 block, upload event] pairs, "turn": which one is next} (frame_records)
         self.engine = Engine(device, h, w, _lib.PIX_F16 if dtype == torch.float16 else _lib.PIX_U8)
-        self.static = settings.static_settings(self.h, self.w)
-        self.engine.set_params(self.static)
         self.lib = self.engine.lib
+        self.set_settings(settings)
+
+    def set_settings(self, settings: RenderSettings):
+        """Replace the render's effect keywords on the ctx this pipeline owns (crtfx_set_params replaces the keyword set): the
+        scanline table of the old settings is dropped; the overlay plane and the glitch staging blocks stay with the pipeline."""
+        self.rs = settings
+        self.static = settings.static_settings(self.h, self.w)
         self._scan_cache = {}
+        self.engine.set_params(self.static)
 
     # ---- per-frame records for frames [first, first+n) -------------------------------------
     def frame_records(self, first: int, n: int, noise_planes: Optional[torch.Tensor] = None):

@@ -164,6 +164,42 @@ def test_reference_built_masks_are_recognised():
     tm[0, 0, 0] = 0.5                                   # rebuilt in place: no longer row-identical
     assert effects._recognise_triad(tm) is tm
     assert len(effects._RECOGNISED) <= effects._RECOGNISED_MAX
+    # ... and none of that rests on [0, 0, 0] being an element the strided sample visits.  What the sample (rows ::h//8, columns
+    # ::w//64) sees of a RECOGNISED array: a rebuild in place with another strength or softness ...
+    rs, cs = max(1, h // 8), max(1, w // 64)
+    off = (1, 1, 0)                                     # off the sampled rows (and columns, where the column stride exceeds 1)
+    assert rs > 1 and off[0] % rs != 0
+    tm, vg = orc.make_triad_mask(h, w, 0.35, 0.5), orc.make_vignette(h, w, 0.25)
+    d, v = effects._recognise_triad(tm), effects._recognise_vignette(vg)
+    assert isinstance(d, effects.TriadMask) and isinstance(v, effects.VignetteMask) and v.strength == 0.25
+    np.copyto(tm, orc.make_triad_mask(h, w, 0.6, 1.4))
+    np.copyto(vg, orc.make_vignette(h, w, 0.5))
+    d2, v2 = effects._recognise_triad(tm), effects._recognise_vignette(vg)
+    assert isinstance(d2, effects.TriadMask) and d2 is not d and d2.key() != d.key() and np.array_equal(np.asarray(d2), tm)
+    assert isinstance(v2, effects.VignetteMask) and v2.strength == 0.5
+    # ... what it does not see: single elements off the sampled rows / columns of a recognised array (the documented limit)
+    before = effects._fingerprint(tm)
+    tm[off] = 0.5
+    assert effects._fingerprint(tm) == before and effects._recognise_triad(tm) is d2
+    tm[rs, 0, 0] = 0.5                                  # ... while one on a sampled row is
+    assert effects._recognise_triad(tm) is tm
+    # a per-pixel plane (an array that is NOT recognised) is compared, all of it, with the host copy of its last upload: any in-place edit is seen
+    for plane, field, idx in ((tm_x, "triad_mask", off), (vg_x, "vignette_mask", off[:2])):
+        kw = {f: None for f in effects.Settings.FIELDS}
+        kw[field] = plane
+        st = effects.Settings(**kw)
+        assert list(st.planes()) == [field] and st.planes()[field] is plane and st.key() == effects.Settings(**kw).key()
+        kept = np.array(plane, copy=True)
+        assert effects._plane_changed(None, plane) and not effects._plane_changed(kept, plane)
+        fp = effects._fingerprint(plane)
+        plane[idx] += 0.125
+        assert effects._fingerprint(plane) == fp and effects._plane_changed(kept, plane), field
+        plane[idx] -= 0.125
+        assert not effects._plane_changed(kept, plane)
+        plane[(0,) * plane.ndim] += 0.125
+        assert effects._plane_changed(kept, plane), field
+        assert effects._plane_changed(kept, plane.astype(np.float16)) and effects._plane_changed(kept[1:], plane)
+    assert effects.Settings(**dict(kw, vignette_mask=effects.make_vignette(h, w, 0.3))).planes() == {}
 
 
 def test_shared_scanline_table_for_integer_phases():
