@@ -14,9 +14,9 @@ LIB_PATH = os.environ.get("CRTFX_LIB") or os.path.join(_HERE, "libcrtfx.so")   #
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = [os.path.join(CSRC, f) for f in ("crtfx.hip", "crtfx_rr.hip", "crtfx_kernels.hip.h", "crtfx_common.hip.h", "crtfx_blur.hip.h", "crtfx_point.hip.h",
                                                 "crtfx_phosphor.hip.h", "crtfx_phosphor_ct.hip.h", "crtfx_warp.hip.h", "crtfx_internal.h", "crtfx_ingest.hip",
-                                                "crtfx_egress.hip", "crtfx_unpack.hip", "crtfx_deep.hip", "crtfx_422.hip", "crtfx_444.hip", "crtfx_stage_host.h")] + \
-          [os.path.join(ROOT, "include", f) for f in ("crtfx.h", "crtfx_ingest.h", "crtfx_egress.h", "crtfx_unpack.h", "crtfx_deep.h", "crtfx_422.h", "crtfx_444.h")]
-STAGE_UNITS = ("crtfx_ingest", "crtfx_egress", "crtfx_unpack", "crtfx_deep", "crtfx_422", "crtfx_444")   # one object file each, beside crtfx.hip / crtfx_rr.hip
+                                                "crtfx_egress.hip", "crtfx_unpack.hip", "crtfx_deep.hip", "crtfx_422.hip", "crtfx_444.hip", "crtfx_sited.hip", "crtfx_stage_host.h")] + \
+          [os.path.join(ROOT, "include", f) for f in ("crtfx.h", "crtfx_ingest.h", "crtfx_egress.h", "crtfx_unpack.h", "crtfx_deep.h", "crtfx_422.h", "crtfx_444.h", "crtfx_sited.h")]
+STAGE_UNITS = ("crtfx_ingest", "crtfx_egress", "crtfx_unpack", "crtfx_deep", "crtfx_422", "crtfx_444", "crtfx_sited")   # one object file each, beside crtfx.hip / crtfx_rr.hip
 RR_RADII = tuple(range(1, 31))      # one register-window build per radius up to 30 (crtfx_internal.h); larger radii: the split path
 
 OK, E_INVALID, E_HIP, E_UNSUPPORTED, E_NOMEM = 0, -1, -2, -3, -4
@@ -143,6 +143,12 @@ UNPACK444_OPT_FORCE_GENERAL = 1
 EGRESS444_OPT_FORCE_GENERAL = 1
 DEEP444_SYMBOLS = stage_symbols("unpack444", "egress444")
 
+# ... and every symbol include/crtfx_sited.h declares (the sited source stage of the seven sub-sampled formats: one handle family, pythoncrt_amd/sited.py)
+SITED_YUV420P, SITED_NV12, SITED_YUV422P, SITED_YUYV422, SITED_UYVY422, SITED_YUV420P10LE, SITED_P010LE = range(7)
+SITED_LEFT, SITED_CENTER = 0, 1
+SITED_OPT_FORCE_GENERAL, SITED_OPT_SITING = 1, 2
+SITED_SYMBOLS = stage_symbols("sited")
+
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC"]
 
 
@@ -222,7 +228,8 @@ def load() -> ctypes.CDLL:
             "`python -c 'import __graft_entry__ as g; g.build()'` (or pythoncrt_amd._lib.build()). "
             "pythoncrt_amd has no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in {**SYMBOLS, **INGEST_SYMBOLS, **EGRESS_SYMBOLS, **UNPACK_SYMBOLS, **DEEP_SYMBOLS, **YUV422_SYMBOLS, **DEEP444_SYMBOLS}.items():
+    for name, (res, args) in {**SYMBOLS, **INGEST_SYMBOLS, **EGRESS_SYMBOLS, **UNPACK_SYMBOLS, **DEEP_SYMBOLS, **YUV422_SYMBOLS, **DEEP444_SYMBOLS,
+                               **SITED_SYMBOLS}.items():
         fn = getattr(lib, name)   # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

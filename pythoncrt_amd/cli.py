@@ -50,6 +50,10 @@ either end independently of the other (include/crtfx_422.h): 2 bytes per pixel, 
       python -m pythoncrt_amd.cli --input - --width 1920 --height 1080 --fps 30 --output - --in-pix-fmt uyvy422 --out-pix-fmt yuv422p [effect flags] |
       ffmpeg -f rawvideo -pix_fmt yuv422p -s 1920x1080 -r 30 -i - out.mov
 
+With a 4:2:0 / 4:2:2 `--in-pix-fmt`, `--in-chroma left` (MPEG-2 / H.264 / HEVC sources: ffprobe's chroma_location=left, or nothing) or
+`--in-chroma center` (JPEG-family sources) interpolates chroma at its siting on the GPU instead of replicating each sample over its pixels
+(UnpackSited, include/crtfx_sited.h); the default `replicate` is the path as it was.
+
 `--gui`, `--gpu`, `--nvenc-preset`, `--encoder`, `--decoder`, `--crf` and `--bitrate` are accepted for
 compatibility and ignored (encode/decode/UI are not part of this path).  `--text*` rasterise the overlay on
 the host with Pillow (ref:366-414) and alpha-blend it on the GPU before or after the effects.
@@ -76,7 +80,7 @@ import time
 
 import numpy as np
 
-from . import formats
+from . import formats, sited
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -171,6 +175,9 @@ def add_input_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
                         "then runs on half pixels")
     p.add_argument("--in-matrix", type=str, default="bt601", choices=["bt601", "bt709"], help="yuv420p / nv12 / 4:2:2 input: the Y'CbCr -> RGB matrix")
     p.add_argument("--in-range", type=str, default="tv", choices=["tv", "pc"], help="yuv420p / nv12 / 4:2:2 input: limited (tv, 16-235) or full (pc) range")
+    p.add_argument("--in-chroma", type=str, default="replicate", choices=["replicate", "left", "center"],
+                   help="4:2:0 / 4:2:2 input: replicate each chroma sample over its pixels (default), or interpolate chroma at its siting on the GPU: "
+                        "left (MPEG-2 / H.264 / HEVC; ffprobe's chroma_location=left or nothing) or center (JPEG-family sources)")
     return p
 
 
@@ -1015,6 +1022,9 @@ def main_sharded(a, rank: int, world: int) -> int:
 
 def main(argv=None) -> int:
     a = add_input_flags(add_output_flags(build_parser())).parse_args(argv)
+    if a.in_chroma != "replicate" and a.in_pix_fmt not in sited.LAYOUTS:
+        raise SystemExit(f"--in-chroma {a.in_chroma} with --in-pix-fmt {a.in_pix_fmt}: only a 4:2:0 or 4:2:2 input has sub-sampled chroma to interpolate "
+                         f"({', '.join(sited.LAYOUTS)})")
     import os as _os
     if int(_os.environ.get("WORLD_SIZE", "1")) > 1 or _os.environ.get("CRTFX_FORCE_DIST") == "1":
         if a.gui or not a.input or a.width <= 0 or a.height <= 0:
@@ -1062,7 +1072,10 @@ def main(argv=None) -> int:
     # frames of in_bytes instead of frame_bytes
     unpack = None
     if a.in_pix_fmt != "rgb24":
-        unpack = formats.FORMATS[a.in_pix_fmt].source(dev, (h, w), layout=a.in_pix_fmt, matrix=a.in_matrix, range=a.in_range)
+        if a.in_chroma == "replicate":
+            unpack = formats.FORMATS[a.in_pix_fmt].source(dev, (h, w), layout=a.in_pix_fmt, matrix=a.in_matrix, range=a.in_range)
+        else:                                                       # chroma interpolated at its siting (include/crtfx_sited.h); the same frames in and out
+            unpack = sited.UnpackSited(dev, (h, w), layout=a.in_pix_fmt, matrix=a.in_matrix, range=a.in_range, siting=a.in_chroma)
     in_bytes = frame_bytes if unpack is None else unpack.frame_bytes
     in_shape = (B, h, w, 3) if unpack is None else (B, in_bytes)
     t0 = time.perf_counter()

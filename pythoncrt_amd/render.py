@@ -20,7 +20,7 @@ from typing import Callable, Iterable, Optional, Tuple
 
 import numpy as np
 
-from . import formats
+from . import formats, sited
 
 # process_video keywords that belong to its container / codec plumbing (out of scope): accepted so that a caller can forward its
 # own keyword dictionary unchanged, and ignored
@@ -91,7 +91,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                    batch: int = 16, noise_seed: Optional[int] = None, device=None, resize_on: str = "device",
                    out_pix_fmt: str = "rgb24", out_matrix: str = "bt601", out_range: str = "tv",
                    in_pix_fmt: str = "rgb24", in_matrix: str = "bt601", in_range: str = "tv", in_size: Optional[Tuple[int, int]] = None,
-                   **io_keywords) -> int:
+                   in_chroma: str = "replicate", **io_keywords) -> int:
     """Render every frame of `frame_iter` (H x W x 3 uint8 RGB arrays) and hand the finished uint8 frames to `write_frame` in order.
     Effect keywords: the names, meaning and defaults of process_video / the CLI (ref:864-911, :1155-1206); the caller applies the clamps of
     ref:1225-1266 as the reference's `main` does (`pythoncrt_amd.cli.settings_from_args` restates them).  Returns the number of frames written.
@@ -129,6 +129,11 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     32-bit arrays of the same bytes are taken too.  The matrix and range keywords apply to yuv444p10le; gbrp10le and x2rgb10le are
     full-range RGB and ignore them.  Refused with ValueError before a device is touched: a 10-bit format on one end only (the 8-bit stages have no half path,
     the 10-bit ones no uint8 path), `in_size` other than the output size (IngestResize has no half path), `resize_on="host"`.
+    `in_chroma="left"` / `"center"` interpolates the chroma of a 4:2:0 / 4:2:2 input at that siting instead of replicating it over its
+    pixels: UnpackSited (include/crtfx_sited.h) then stands where the family's source plan stood — in front of the half chain for
+    "yuv420p10le" / "p010le", in front of IngestResize for an off-size 8-bit source.  "left" is the siting of MPEG-2 / H.264 / HEVC streams,
+    "center" that of JPEG-family sources; "replicate" (default) is the path as it was.  Refused with ValueError before a device is touched:
+    an unknown value, and "left" / "center" with "rgb24" or a 4:4:4 format (there is nothing to interpolate).
     If `frame_iter` or `write_frame` raises, the GPU work already queued is drained (device synchronize) before the exception leaves this
     function, so that the staging buffers are not freed under a running copy."""
     import os
@@ -145,6 +150,11 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     if in_pix_fmt not in formats.PIX_FMTS:
         raise ValueError("in_pix_fmt must be 'rgb24', 'yuv420p' or 'nv12', 'yuv422p', 'yuyv422' or 'uyvy422' (or, with a 10-bit output, "
                          f"'yuv420p10le' or 'p010le', 'yuv444p10le', 'gbrp10le' or 'x2rgb10le'), got {in_pix_fmt!r}")
+    if in_chroma not in ("replicate", "left", "center"):
+        raise ValueError(f"in_chroma must be 'replicate', 'left' or 'center', got {in_chroma!r}")
+    if in_chroma != "replicate" and in_pix_fmt not in sited.LAYOUTS:
+        raise ValueError(f"in_chroma={in_chroma!r} with in_pix_fmt={in_pix_fmt!r}: only a 4:2:0 or 4:2:2 input has sub-sampled chroma to "
+                         f"interpolate ({', '.join(sited.LAYOUTS)})")
     deep = formats.bits(in_pix_fmt) == 10                                      # both ends or neither
     if deep != (formats.bits(out_pix_fmt) == 10):
         raise ValueError(f"in_pix_fmt={in_pix_fmt!r} with out_pix_fmt={out_pix_fmt!r}: a 10-bit format on one end only — the chain between "
@@ -225,7 +235,10 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         """Staging of a 4:2:0 or 4:2:2 input: pinned and device slots of frame_bytes(*in_size) bytes per frame, the plan that converts them to RGB —
         into dev_in[d] itself, or, where in_size is not the output size, into RGB slots of that size which IngestResize brings to dev_in[d]."""
         def __init__(self):
-            self.plan = formats.FORMATS[in_pix_fmt].source(dev, yuv_hw, layout=in_pix_fmt, matrix=in_matrix, range=in_range)
+            if in_chroma == "replicate":
+                self.plan = formats.FORMATS[in_pix_fmt].source(dev, yuv_hw, layout=in_pix_fmt, matrix=in_matrix, range=in_range)
+            else:
+                self.plan = sited.UnpackSited(dev, yuv_hw, layout=in_pix_fmt, matrix=in_matrix, range=in_range, siting=in_chroma)
             self.nbytes = self.plan.frame_bytes
             assert self.nbytes == yuv_bytes
             self.resize, self.rgb = None, None
