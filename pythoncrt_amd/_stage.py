@@ -1,4 +1,4 @@
-"""What the ten format-stage plans (unpack.py, egress.py, deep.py, yuv422.py, deep444.py) and the sited source plan (sited.py) share: the handle of one crtfx_<family>_* family
+"""What the ten format-stage plans (unpack.py, egress.py, deep.py, yuv422.py, deep444.py) and the two sited plans (sited.py: source and egress) share: the handle of one crtfx_<family>_* family
 (seven entry points, `_lib.stage_symbols`) behind a plan object.  A family module declares two short classes on `SourcePlan` / `EgressPlan`
 — family name, C layout numbers, table function, RGB dtype, frame size — and keeps its layout helpers; everything else is here."""
 from __future__ import annotations

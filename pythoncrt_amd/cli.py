@@ -54,6 +54,11 @@ With a 4:2:0 / 4:2:2 `--in-pix-fmt`, `--in-chroma left` (MPEG-2 / H.264 / HEVC s
 `--in-chroma center` (JPEG-family sources) interpolates chroma at its siting on the GPU instead of replicating each sample over its pixels
 (UnpackSited, include/crtfx_sited.h); the default `replicate` is the path as it was.
 
+With a 4:2:0 / 4:2:2 `--out-pix-fmt`, `--out-chroma left` filters every chroma sample onto its first luma column on the GPU
+(EgressSited, include/crtfx_egress_sited.h) — the siting ffmpeg's muxers tag or assume for such a file, what ffprobe then reports as
+chroma_location=left (or nothing) and the only siting 4:2:2 defines; pass `-chroma_sample_location left` to the encoder.  The default
+`center` writes the 2 x 2 / 2 x 1 box mean as before (ffprobe's chroma_location=center: JPEG / MPEG-1).
+
 `--gui`, `--gpu`, `--nvenc-preset`, `--encoder`, `--decoder`, `--crf` and `--bitrate` are accepted for
 compatibility and ignored (encode/decode/UI are not part of this path).  `--text*` rasterise the overlay on
 the host with Pillow (ref:366-414) and alpha-blend it on the GPU before or after the effects.
@@ -162,6 +167,9 @@ def add_output_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
                         "then runs on half pixels")
     p.add_argument("--out-matrix", type=str, default="bt601", choices=["bt601", "bt709"], help="yuv420p / nv12 / 4:2:2: the RGB -> Y'CbCr matrix")
     p.add_argument("--out-range", type=str, default="tv", choices=["tv", "pc"], help="yuv420p / nv12 / 4:2:2: limited (tv, 16-235) or full (pc) range")
+    p.add_argument("--out-chroma", type=str, default="center", choices=["center", "left"],
+                   help="4:2:0 / 4:2:2 output: write chroma as the box mean of its pixels (center, default: ffprobe's chroma_location=center), or filter it "
+                        "onto its first luma column on the GPU (left: MPEG-2 / H.264 / HEVC and every 4:2:2 format; ffprobe's chroma_location=left or nothing)")
     return p
 
 
@@ -1025,6 +1033,9 @@ def main(argv=None) -> int:
     if a.in_chroma != "replicate" and a.in_pix_fmt not in sited.LAYOUTS:
         raise SystemExit(f"--in-chroma {a.in_chroma} with --in-pix-fmt {a.in_pix_fmt}: only a 4:2:0 or 4:2:2 input has sub-sampled chroma to interpolate "
                          f"({', '.join(sited.LAYOUTS)})")
+    if a.out_chroma != "center" and a.out_pix_fmt not in sited.LAYOUTS:
+        raise SystemExit(f"--out-chroma {a.out_chroma} with --out-pix-fmt {a.out_pix_fmt}: only a 4:2:0 or 4:2:2 output has chroma to down-sample "
+                         f"({', '.join(sited.LAYOUTS)})")
     import os as _os
     if int(_os.environ.get("WORLD_SIZE", "1")) > 1 or _os.environ.get("CRTFX_FORCE_DIST") == "1":
         if a.gui or not a.input or a.width <= 0 or a.height <= 0:
@@ -1064,7 +1075,10 @@ def main(argv=None) -> int:
     # and pinned output slots, the download, the output file's offsets and size — is in frames of out_bytes instead of frame_bytes
     egress = None
     if a.out_pix_fmt != "rgb24":
-        egress = formats.FORMATS[a.out_pix_fmt].egress(dev, (h, w), layout=a.out_pix_fmt, matrix=a.out_matrix, range=a.out_range)
+        if a.out_chroma == "center":
+            egress = formats.FORMATS[a.out_pix_fmt].egress(dev, (h, w), layout=a.out_pix_fmt, matrix=a.out_matrix, range=a.out_range)
+        else:                                                       # chroma filtered onto its siting (include/crtfx_egress_sited.h); the same frames in and out
+            egress = sited.EgressSited(dev, (h, w), layout=a.out_pix_fmt, matrix=a.out_matrix, range=a.out_range, siting=a.out_chroma)
     out_bytes = frame_bytes if egress is None else egress.frame_bytes
     out_shape = (B, h, w, 3) if egress is None else (B, out_bytes)
     # --in-pix-fmt yuv420p / nv12 / yuv422p / yuyv422 / uyvy422, the mirror image: the frames are converted to RGB on the device in front of the chain (UnpackYuv) and

@@ -91,7 +91,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                    batch: int = 16, noise_seed: Optional[int] = None, device=None, resize_on: str = "device",
                    out_pix_fmt: str = "rgb24", out_matrix: str = "bt601", out_range: str = "tv",
                    in_pix_fmt: str = "rgb24", in_matrix: str = "bt601", in_range: str = "tv", in_size: Optional[Tuple[int, int]] = None,
-                   in_chroma: str = "replicate", **io_keywords) -> int:
+                   in_chroma: str = "replicate", out_chroma: str = "center", **io_keywords) -> int:
     """Render every frame of `frame_iter` (H x W x 3 uint8 RGB arrays) and hand the finished uint8 frames to `write_frame` in order.
     Effect keywords: the names, meaning and defaults of process_video / the CLI (ref:864-911, :1155-1206); the caller applies the clamps of
     ref:1225-1266 as the reference's `main` does (`pythoncrt_amd.cli.settings_from_args` restates them).  Returns the number of frames written.
@@ -134,6 +134,11 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     "yuv420p10le" / "p010le", in front of IngestResize for an off-size 8-bit source.  "left" is the siting of MPEG-2 / H.264 / HEVC streams,
     "center" that of JPEG-family sources; "replicate" (default) is the path as it was.  Refused with ValueError before a device is touched:
     an unknown value, and "left" / "center" with "rgb24" or a 4:4:4 format (there is nothing to interpolate).
+    `out_chroma="left"` filters the chroma of a 4:2:0 / 4:2:2 output onto the siting ffmpeg's muxers tag or assume (chroma_location=left:
+    the sample on its first luma column, [1 2 1] / 4 around it) instead of writing the 2 x 2 / 2 x 1 box mean, which is centre siting:
+    EgressSited (include/crtfx_egress_sited.h) then stands where the family's egress plan stood — behind the half chain for "yuv420p10le" /
+    "p010le".  "center" (default) is the path as it was: the family's own plan, plan string and bytes.  Refused with ValueError before a
+    device is touched: an unknown value, and "left" with "rgb24" or a 4:4:4 format (there is nothing to down-sample).
     If `frame_iter` or `write_frame` raises, the GPU work already queued is drained (device synchronize) before the exception leaves this
     function, so that the staging buffers are not freed under a running copy."""
     import os
@@ -155,6 +160,11 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     if in_chroma != "replicate" and in_pix_fmt not in sited.LAYOUTS:
         raise ValueError(f"in_chroma={in_chroma!r} with in_pix_fmt={in_pix_fmt!r}: only a 4:2:0 or 4:2:2 input has sub-sampled chroma to "
                          f"interpolate ({', '.join(sited.LAYOUTS)})")
+    if out_chroma not in ("center", "left"):
+        raise ValueError(f"out_chroma must be 'center' or 'left', got {out_chroma!r}")
+    if out_chroma != "center" and out_pix_fmt not in sited.LAYOUTS:
+        raise ValueError(f"out_chroma={out_chroma!r} with out_pix_fmt={out_pix_fmt!r}: only a 4:2:0 or 4:2:2 output has chroma to "
+                         f"down-sample ({', '.join(sited.LAYOUTS)})")
     deep = formats.bits(in_pix_fmt) == 10                                      # both ends or neither
     if deep != (formats.bits(out_pix_fmt) == 10):
         raise ValueError(f"in_pix_fmt={in_pix_fmt!r} with out_pix_fmt={out_pix_fmt!r}: a 10-bit format on one end only — the chain between "
@@ -193,7 +203,10 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
               for _ in range(NS)]
     egress = None
     if out_pix_fmt != "rgb24":                                                 # the encoder's format: converted on the device, half the bytes downloaded
-        egress = formats.FORMATS[out_pix_fmt].egress(dev, (h, w), layout=out_pix_fmt, matrix=out_matrix, range=out_range)
+        if out_chroma == "center":
+            egress = formats.FORMATS[out_pix_fmt].egress(dev, (h, w), layout=out_pix_fmt, matrix=out_matrix, range=out_range)
+        else:
+            egress = sited.EgressSited(dev, (h, w), layout=out_pix_fmt, matrix=out_matrix, range=out_range, siting=out_chroma)
     out_shape = (B, h, w, 3) if egress is None else (B, egress.frame_bytes)    # what is downloaded and handed to the writer
     pin_out = [torch.empty(out_shape, dtype=torch.uint8).pin_memory() for _ in range(NS)]
     dev_in = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]

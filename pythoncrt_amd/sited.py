@@ -3,13 +3,18 @@ with the chroma planes interpolated at a stated siting instead of replicated ove
 decoders hand out (ffprobe's chroma_location=left, or nothing), "center" for JPEG-family sources.  It stands where UnpackYuv, UnpackYuv422
 and UnpackYuv10 stand — the same packed frames in, the same RGB frames out (uint8, or half for the two 10-bit layouts) — and gives their
 bytes wherever the chroma taps of a pixel are equal (include/crtfx_sited.h holds the arithmetic and the two kernel paths).  The matrices
-are those stages' (tables.rgb_matrix / tables.rgb_matrix10).  Not byte-equal to libswscale — see the header."""
+are those stages' (tables.rgb_matrix / tables.rgb_matrix10).  Not byte-equal to libswscale — see the header.
+
+`EgressSited` — its mirror image behind the chain: finished RGB frames to the same seven formats with every chroma sample filtered onto the
+stated siting ([1 2 1] / 4 around luma column 2 cx for "left") instead of taken as the box mean, which is centre siting.  It stands where
+EgressYuv, EgressYuv422 and EgressYuv10 stand and gives their bytes, for every input, with siting="center"
+(include/crtfx_egress_sited.h).  The matrices are those stages' (tables.yuv_matrix / tables.yuv_matrix10)."""
 from __future__ import annotations
 
 from typing import Tuple
 
 from . import _lib, deep, egress, tables, yuv422
-from ._stage import SourcePlan
+from ._stage import EgressPlan, SourcePlan
 
 LAYOUTS = {"yuv420p": _lib.SITED_YUV420P, "nv12": _lib.SITED_NV12, "yuv422p": _lib.SITED_YUV422P, "yuyv422": _lib.SITED_YUYV422,
            "uyvy422": _lib.SITED_UYVY422, "yuv420p10le": _lib.SITED_YUV420P10LE, "p010le": _lib.SITED_P010LE}
@@ -72,3 +77,42 @@ class UnpackSited(SourcePlan):
         if value not in SITINGS:
             raise ValueError(f"siting must be one of {sorted(SITINGS)}, got {value!r}")
         self.set_option(_lib.SITED_OPT_SITING, SITINGS[value])
+
+
+class EgressSited(EgressPlan):
+    """plan = EgressSited(device, (h, w), layout, matrix="bt601", range="tv", siting="left"); out = plan.run(frames[n, h, w, 3]) ->
+    uint8[n, frame_bytes]; `frames` are uint8, or float16 on the 0..255 scale for "yuv420p10le" / "p010le".  `frames` and `out` are tensors
+    on `device` whose frames are contiguous (the batch stride is free; 10-bit: bases and strides must be even).  `plan.siting = "center"`
+    switches a live plan to the box stages' bytes.  The work is enqueued on the current stream of `device`; nothing synchronises."""
+    _family, _force_option, _layouts = "egress_sited", _lib.EGRESS_SITED_OPT_FORCE_GENERAL, LAYOUTS
+    _frame_bytes, _split_planes = frame_bytes, split_planes
+
+    def __init__(self, device, size: Tuple[int, int], layout: str, matrix: str = "bt601", range: str = "tv", siting: str = "left",    # noqa: A002
+                 force_general: bool = False):
+        if siting not in SITINGS:
+            raise ValueError(f"siting must be one of {sorted(SITINGS)}, got {siting!r}")
+        ten = layout in deep.LAYOUTS
+        self._rgb = "float16" if ten else "uint8"
+        self._siting = "left"
+        super().__init__(device, size, layout, matrix, range, _lib.PIX_F16 if ten else _lib.PIX_U8, force_general)
+        if siting != "left":
+            self.siting = siting
+
+    def _tables(self):
+        return (tables.yuv_matrix10 if self.layout in deep.LAYOUTS else tables.yuv_matrix)(self.matrix, self.range)
+
+    def set_option(self, option: int, value: int) -> None:
+        super().set_option(option, value)
+        if int(option) == _lib.EGRESS_SITED_OPT_SITING:
+            self._siting = "center" if int(value) == _lib.SITED_CENTER else "left"
+
+    @property
+    def siting(self) -> str:
+        """"left" or "center": where a chroma sample sits against its two luma columns (CRTFX_EGRESS_SITED_OPT_SITING)."""
+        return self._siting
+
+    @siting.setter
+    def siting(self, value: str) -> None:
+        if value not in SITINGS:
+            raise ValueError(f"siting must be one of {sorted(SITINGS)}, got {value!r}")
+        self.set_option(_lib.EGRESS_SITED_OPT_SITING, SITINGS[value])
