@@ -170,7 +170,23 @@ def add_output_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--out-chroma", type=str, default="center", choices=["center", "left"],
                    help="4:2:0 / 4:2:2 output: write chroma as the box mean of its pixels (center, default: ffprobe's chroma_location=center), or filter it "
                         "onto its first luma column on the GPU (left: MPEG-2 / H.264 / HEVC and every 4:2:2 format; ffprobe's chroma_location=left or nothing)")
+    p.add_argument("--deliver-width", type=int, default=0,
+                   help="width of the frames written, with --deliver-height: the frames are rendered at --width x --height and resized on the GPU behind "
+                        "the chain (a 4K render written as 1080p); 0 (default) = as rendered")
+    p.add_argument("--deliver-height", type=int, default=0, help="height of the frames written (see --deliver-width); 0 (default) = as rendered")
     return p
+
+
+def deliver_size_from_args(a):
+    """(dh, dw) of --deliver-height / --deliver-width, or None where the frames are written as rendered.  Both flags, or neither."""
+    dw, dh = int(getattr(a, "deliver_width", 0) or 0), int(getattr(a, "deliver_height", 0) or 0)
+    if (dw == 0) != (dh == 0):
+        raise SystemExit("--deliver-width and --deliver-height go together: pass both, or neither (0 = as rendered)")
+    if dw == 0:
+        return None
+    if min(dh, dw) < 1 or max(dh, dw) > 32767:
+        raise SystemExit(f"--deliver-width {dw} --deliver-height {dh}: sizes outside 1..32767")
+    return None if (dh, dw) == (int(a.height), int(a.width)) else (dh, dw)
 
 
 def add_input_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
@@ -894,6 +910,10 @@ def main_sharded(a, rank: int, world: int) -> int:
     the clip's chunks of --batch frames are dealt round-robin over the ranks, each rank reads its chunks
     from the raw input file and writes them at the same offsets of the output file; with --persistence > 0 one
     float32 state frame per chunk boundary travels to the next rank (RCCL)."""
+    if getattr(a, "deliver_width", 0) or getattr(a, "deliver_height", 0):
+        # every rank writes its chunks at offsets of its own: those, and the downloads behind them, are at render size here
+        raise SystemExit("--deliver-width / --deliver-height are not supported by the sharded CLI (one process per GPU writes rgb24 at render size); "
+                         "run one process, or scale behind it")
     if getattr(a, "out_pix_fmt", "rgb24") != "rgb24":
         # every rank writes its chunks at offsets of its own: those, and the downloads behind them, are rgb24-sized here
         raise SystemExit(f"--out-pix-fmt {a.out_pix_fmt} is not supported by the sharded CLI (one process per GPU writes rgb24 only); "
@@ -1036,6 +1056,7 @@ def main(argv=None) -> int:
     if a.out_chroma != "center" and a.out_pix_fmt not in sited.LAYOUTS:
         raise SystemExit(f"--out-chroma {a.out_chroma} with --out-pix-fmt {a.out_pix_fmt}: only a 4:2:0 or 4:2:2 output has chroma to down-sample "
                          f"({', '.join(sited.LAYOUTS)})")
+    deliver = deliver_size_from_args(a)                             # None: written as rendered
     import os as _os
     if int(_os.environ.get("WORLD_SIZE", "1")) > 1 or _os.environ.get("CRTFX_FORCE_DIST") == "1":
         if a.gui or not a.input or a.width <= 0 or a.height <= 0:
@@ -1071,16 +1092,28 @@ def main(argv=None) -> int:
     out_path = a.output if a.output else (a.input + "_crt.rgb" if a.input != "-" else "-")
     B = max(1, int(a.batch))
     frame_bytes = h * w * 3
+    # --deliver-width / --deliver-height: the chain's frames are resized on the device behind it (IngestResize for uint8 frames, ResizeHalf for
+    # half ones) and everything downstream — the egress plan, the output slots, the download, the output file's offsets and size — is in
+    # frames of dh x dw
+    dh, dw = deliver if deliver is not None else (h, w)
+    resize_out = None
+    if deliver is not None:
+        if deep:
+            from .resize16 import ResizeHalf
+            resize_out = ResizeHalf(dev, (h, w), (dh, dw))
+        else:
+            from .ingest import IngestResize
+            resize_out = IngestResize(dev, (h, w), (dh, dw))
     # --out-pix-fmt yuv420p / nv12 / yuv422p / yuyv422 / uyvy422: the chain's frames are converted on the device behind it (EgressYuv) and everything downstream — the device
     # and pinned output slots, the download, the output file's offsets and size — is in frames of out_bytes instead of frame_bytes
     egress = None
     if a.out_pix_fmt != "rgb24":
         if a.out_chroma == "center":
-            egress = formats.FORMATS[a.out_pix_fmt].egress(dev, (h, w), layout=a.out_pix_fmt, matrix=a.out_matrix, range=a.out_range)
+            egress = formats.FORMATS[a.out_pix_fmt].egress(dev, (dh, dw), layout=a.out_pix_fmt, matrix=a.out_matrix, range=a.out_range)
         else:                                                       # chroma filtered onto its siting (include/crtfx_egress_sited.h); the same frames in and out
-            egress = sited.EgressSited(dev, (h, w), layout=a.out_pix_fmt, matrix=a.out_matrix, range=a.out_range, siting=a.out_chroma)
-    out_bytes = frame_bytes if egress is None else egress.frame_bytes
-    out_shape = (B, h, w, 3) if egress is None else (B, out_bytes)
+            egress = sited.EgressSited(dev, (dh, dw), layout=a.out_pix_fmt, matrix=a.out_matrix, range=a.out_range, siting=a.out_chroma)
+    out_bytes = dh * dw * 3 if egress is None else egress.frame_bytes
+    out_shape = (B, dh, dw, 3) if egress is None else (B, out_bytes)
     # --in-pix-fmt yuv420p / nv12 / yuv422p / yuyv422 / uyvy422, the mirror image: the frames are converted to RGB on the device in front of the chain (UnpackYuv) and
     # everything upstream — the reader's frame size, the input's length in frames, the pinned and device input slots, the upload — is in
     # frames of in_bytes instead of frame_bytes
@@ -1130,7 +1163,8 @@ def main(argv=None) -> int:
     dev_in = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]
     dev_out = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]
     dev_recv = dev_in if unpack is None else [torch.empty(in_shape, dtype=torch.uint8, device=dev) for _ in range(NS)]         # what is uploaded
-    dev_send = dev_out if egress is None else [torch.empty(out_shape, dtype=torch.uint8, device=dev) for _ in range(NS)]      # what is downloaded
+    dev_fin = dev_out if resize_out is None else [torch.empty((B, dh, dw, 3), dtype=pix, device=dev) for _ in range(NS)]    # what the egress plan reads
+    dev_send = dev_fin if egress is None else [torch.empty(out_shape, dtype=torch.uint8, device=dev) for _ in range(NS)]      # what is downloaded
     compute = torch.cuda.current_stream(dev)
     s_up, s_down = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
     kernels_done = [None] * NS                                      # per device slot: its batch's kernels have finished (dev_in free again)
@@ -1167,8 +1201,10 @@ def main(argv=None) -> int:
                 if unpack is not None:                            # on the compute stream, behind the upload and behind the chain that last read
                     unpack.run(dev_recv[d][:n], out=dev_in[d][:n])    # dev_in[d] (batch k - NS, same stream): counted with the kernels below
                 _, state = pipe.run(dev_in[d][:n], first_index=index, state=state, out=dev_out[d][:n])
+                if resize_out is not None:                        # on the compute stream, behind the chain and behind the download that last
+                    resize_out.run(dev_out[d][:n], out=dev_fin[d][:n])    # read this slot (awaited above): counted with the kernels below
                 if egress is not None:                            # on the compute stream, behind the chain: counted with the kernels below
-                    egress.run(dev_out[d][:n], out=dev_send[d][:n])
+                    egress.run(dev_fin[d][:n], out=dev_send[d][:n])
                 kd = torch.cuda.Event(enable_timing=tim)
                 kd.record(compute)
                 kernels_done[d] = kd

@@ -77,6 +77,23 @@ def iter_deep444(stream, w: int, h: int, fmt: str):
     return _iter_frames(stream, formats.DEEP444.frame_bytes(int(h), int(w), fmt))
 
 
+def parse_deliver_size(deliver_size, out_h: int, out_w: int) -> Optional[Tuple[int, int]]:
+    """(dh, dw) of `process_frames(deliver_size=)`, or None where the frames are delivered as rendered (None, or the render size itself).
+    ValueError: not a pair of integers, a size < 1 or > 32767."""
+    if deliver_size is None:
+        return None
+    try:
+        dh, dw = deliver_size
+        if isinstance(dh, bool) or isinstance(dw, bool) or int(dh) != dh or int(dw) != dw:
+            raise TypeError
+        dh, dw = int(dh), int(dw)
+    except (TypeError, ValueError):
+        raise ValueError(f"deliver_size must be a pair (height, width) of integers, got {deliver_size!r}") from None
+    if min(dh, dw) < 1 or max(dh, dw) > 32767:
+        raise ValueError(f"deliver_size={deliver_size!r}: sizes outside 1..32767")
+    return None if (dh, dw) == (int(out_h), int(out_w)) else (dh, dw)
+
+
 def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.ndarray], None], out_w: int, out_h: int, fps_out: float,
                    total_frames: Optional[int] = None, *,
                    scanline_strength: float = 0.6, triad_strength: float = 0.35, triad_gamma: float = 2.2, triad_preserve_luma: bool = False,
@@ -91,7 +108,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                    batch: int = 16, noise_seed: Optional[int] = None, device=None, resize_on: str = "device",
                    out_pix_fmt: str = "rgb24", out_matrix: str = "bt601", out_range: str = "tv",
                    in_pix_fmt: str = "rgb24", in_matrix: str = "bt601", in_range: str = "tv", in_size: Optional[Tuple[int, int]] = None,
-                   in_chroma: str = "replicate", out_chroma: str = "center", **io_keywords) -> int:
+                   in_chroma: str = "replicate", out_chroma: str = "center", deliver_size: Optional[Tuple[int, int]] = None, **io_keywords) -> int:
     """Render every frame of `frame_iter` (H x W x 3 uint8 RGB arrays) and hand the finished uint8 frames to `write_frame` in order.
     Effect keywords: the names, meaning and defaults of process_video / the CLI (ref:864-911, :1155-1206); the caller applies the clamps of
     ref:1225-1266 as the reference's `main` does (`pythoncrt_amd.cli.settings_from_args` restates them).  Returns the number of frames written.
@@ -139,6 +156,15 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     EgressSited (include/crtfx_egress_sited.h) then stands where the family's egress plan stood — behind the half chain for "yuv420p10le" /
     "p010le".  "center" (default) is the path as it was: the family's own plan, plan string and bytes.  Refused with ValueError before a
     device is touched: an unknown value, and "left" with "rgb24" or a 4:4:4 format (there is nothing to down-sample).
+    `deliver_size=(dh, dw)` writes the frames at another size than they are rendered at (a 4K render delivered as 1080p: scanlines and the
+    triad mask have periods of 2 and 3 pixels, and a render at the delivery resolution shows moire that a render at twice the size does not).
+    The chain runs at out_h x out_w exactly as without it — text overlay, persistence state and grain are at render size; behind it the
+    finished frames are resized on the device, uint8 ones by IngestResize (Pillow's BILINEAR bytes of the rendered frame), half ones by
+    ResizeHalf (include/crtfx_resize16.h: the same resampler on quarter codes); behind that stands the egress plan of `out_pix_fmt`, built
+    for (dh, dw).  The download and the arrays handed to `write_frame` have the delivery size (dh x dw x 3 for "rgb24", else
+    frame_bytes(dh, dw) bytes).  `None` (default) and the render size itself are the path as it was: no resize plan is created.  Refused
+    with ValueError before a device is touched: a value that is not a pair of integers, a size < 1 or > 32767.  (`in_size` for a 10-bit
+    input stays refused: the source side of the half chain has no resize.)
     If `frame_iter` or `write_frame` raises, the GPU work already queued is drained (device synchronize) before the exception leaves this
     function, so that the staging buffers are not freed under a running copy."""
     import os
@@ -174,10 +200,12 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                          "resized (IngestResize has no half path)")
     if in_pix_fmt != "rgb24" and resize_on == "host":
         raise ValueError(f"resize_on='host' cannot be combined with in_pix_fmt={in_pix_fmt!r}: there is no host RGB frame to hand to Pillow")
+    deliver = parse_deliver_size(deliver_size, int(out_h), int(out_w))         # None: delivered as rendered
     if not torch.cuda.is_available():
         raise RuntimeError("no ROCm device visible; pythoncrt_amd has no CPU fallback")
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     h, w, B = int(out_h), int(out_w), max(1, int(batch))
+    dh, dw = deliver if deliver is not None else (h, w)
     rs = RenderSettings(
         scanline_strength=float(scanline_strength), triad_strength=float(triad_strength), triad_gamma=float(triad_gamma),
         triad_preserve_luma=bool(triad_preserve_luma), triad_softness=float(triad_softness), aberration_px=int(aberration_px),
@@ -204,13 +232,22 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     egress = None
     if out_pix_fmt != "rgb24":                                                 # the encoder's format: converted on the device, half the bytes downloaded
         if out_chroma == "center":
-            egress = formats.FORMATS[out_pix_fmt].egress(dev, (h, w), layout=out_pix_fmt, matrix=out_matrix, range=out_range)
+            egress = formats.FORMATS[out_pix_fmt].egress(dev, (dh, dw), layout=out_pix_fmt, matrix=out_matrix, range=out_range)
         else:
-            egress = sited.EgressSited(dev, (h, w), layout=out_pix_fmt, matrix=out_matrix, range=out_range, siting=out_chroma)
-    out_shape = (B, h, w, 3) if egress is None else (B, egress.frame_bytes)    # what is downloaded and handed to the writer
+            egress = sited.EgressSited(dev, (dh, dw), layout=out_pix_fmt, matrix=out_matrix, range=out_range, siting=out_chroma)
+    out_shape = (B, dh, dw, 3) if egress is None else (B, egress.frame_bytes)  # what is downloaded and handed to the writer
+    resize_out = None
+    if deliver is not None:                                                    # the finished frames at the delivery size, between the chain and the egress plan
+        if deep:
+            from .resize16 import ResizeHalf
+            resize_out = ResizeHalf(dev, (h, w), (dh, dw))
+        else:
+            from .ingest import IngestResize
+            resize_out = IngestResize(dev, (h, w), (dh, dw))
     pin_out = [torch.empty(out_shape, dtype=torch.uint8).pin_memory() for _ in range(NS)]
     dev_in = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]
     dev_out = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]
+    dev_fin = dev_out if resize_out is None else [torch.empty((B, dh, dw, 3), dtype=pix, device=dev) for _ in range(NS)]   # what the egress plan / the download reads
     dev_yuv = [torch.empty(out_shape, dtype=torch.uint8, device=dev) for _ in range(NS)] if egress is not None else None
     np_in = [t.numpy() for t in pin_in]
     np_out = [t.numpy() for t in pin_out]
@@ -365,8 +402,10 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                 if down_done[d] is not None:
                     compute.wait_event(down_done[d])
                 _, state = pipe.run(dev_in[d][:n], first_index=index, state=state, out=dev_out[d][:n])
+                if resize_out is not None:           # behind the chain on the compute stream; dev_fin[d]'s last reader (egress on this stream, or
+                    resize_out.run(dev_out[d][:n], out=dev_fin[d][:n])    # the download awaited above) is done
                 if egress is not None:               # behind the chain on the compute stream; dev_yuv[d]'s last download was awaited above
-                    egress.run(dev_out[d][:n], out=dev_yuv[d][:n])
+                    egress.run(dev_fin[d][:n], out=dev_yuv[d][:n])
                 kd = torch.cuda.Event()
                 kd.record(compute)
                 kernels_done[d] = kd
@@ -375,7 +414,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                 # pin_out[d] was drained one iteration ago (drain below runs before the next batch is enqueued into the same slot)
                 s_down.wait_event(kd)
                 with torch.cuda.stream(s_down):
-                    pin_out[d][:n].copy_((dev_out if egress is None else dev_yuv)[d][:n], non_blocking=True)
+                    pin_out[d][:n].copy_((dev_fin if egress is None else dev_yuv)[d][:n], non_blocking=True)
                     dn = torch.cuda.Event()
                     dn.record(s_down)
                 down_done[d] = dn

@@ -5,7 +5,8 @@ PCIe both ways, the per-frame write_frame call).
     python tools/process_frames_rate.py                                           # 1080p and 4K, source at the output size, both settings
     python tools/process_frames_rate.py --size 2160x3840 --source 1080x1920       # a 1080p source rendered at 4K (resized on the device)
     python tools/process_frames_rate.py --size 2160x3840 --source 1080x1920 --resize-on host --frames 48     # ... by Pillow on the host
-    options: --frames N (per repeat), --repeats R, --chain full|default|both"""
+    python tools/process_frames_rate.py --size 2160x3840 --out-pix-fmt yuv420p --deliver 1080x1920            # a 4K render delivered as 1080p yuv420p
+    options: --frames N (per repeat), --repeats R, --chain full|default|both, --out-pix-fmt FMT, --deliver HxW (process_frames(deliver_size=))"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -28,6 +29,10 @@ size, source, resize_on = opt("--size"), opt("--source"), opt("--resize-on")
 sizes = [hw(size) + (int(opt("--frames", 160)),)] if size else [(1080, 1920, int(opt("--frames", 480))), (2160, 3840, int(opt("--frames", 160)))]
 chains = [CHAINS[c] for c in (("default", "full") if opt("--chain", "both") == "both" else (opt("--chain"),))]
 extra = {"resize_on": resize_on} if resize_on else {}          # absent: the package's default
+if opt("--out-pix-fmt"):
+    extra["out_pix_fmt"] = opt("--out-pix-fmt")
+if opt("--deliver"):
+    extra["deliver_size"] = hw(opt("--deliver"))
 for (h, w, n) in sizes:
     sh, sw = hw(source) if source else (h, w)
     rng = np.random.default_rng(0)
@@ -39,4 +44,7 @@ for (h, w, n) in sizes:
             k = pc.process_frames((base[i % 8] for i in range(n)), lambda a: None, w, h, 30, n, noise_seed=1, **kw, **extra)
             dt = time.perf_counter() - t
             src = "" if (sh, sw) == (h, w) else f" from a {sw}x{sh} source (resize_on={resize_on or 'default'})"
+            if "deliver_size" in extra or "out_pix_fmt" in extra:
+                dh, dw = extra.get("deliver_size", (h, w))
+                src += f" written as {dw}x{dh} {extra.get('out_pix_fmt', 'rgb24')}"
             print(f"{w}x{h}{src} {name}: {k} frames in {dt:.3f} s = {k / dt:.0f} frames/s (set-up of the call included)", flush=True)
