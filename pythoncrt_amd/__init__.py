@@ -11,6 +11,7 @@
     from pythoncrt_amd import UnpackSited         # the source step of every 4:2:0 / 4:2:2 format with chroma interpolated at its siting ("left" / "center")
     from pythoncrt_amd import EgressSited         # ... and the egress step of the same formats with chroma filtered onto that siting instead of box-averaged
     from pythoncrt_amd import ResizeHalf          # IngestResize for half frames: behind the chain, where process_frames(deliver_size=) delivers another size
+    from pythoncrt_amd import Resample            # either of the two with a filter: box / bilinear / hamming / bicubic / lanczos, uint8 or half frames
 
 See DESIGN.md (path, kernels, roofline) and INTEGRATION.md (how the reference binds to it).
 """
@@ -21,6 +22,7 @@ from .deep444 import EgressDeep444, UnpackDeep444
 from .egress import EgressYuv
 from .ingest import IngestResize
 from .resize16 import ResizeHalf
+from .resample import Resample
 from .render import iter_deep444, iter_rgb24, iter_yuv420, iter_yuv422, process_frames
 from .sited import EgressSited, UnpackSited
 from .unpack import UnpackYuv
@@ -28,4 +30,4 @@ from .yuv422 import EgressYuv422, UnpackYuv422
 
 __all__ = ["DeviceState", "TriadMask", "VignetteMask", "apply_crt_effect", "apply_static_effects", "make_triad_mask", "make_vignette",
            "process_frames", "iter_rgb24", "iter_yuv420", "IngestResize", "EgressYuv", "UnpackYuv", "EgressYuv10", "UnpackYuv10",
-           "iter_yuv422", "EgressYuv422", "UnpackYuv422", "iter_deep444", "EgressDeep444", "UnpackDeep444", "UnpackSited", "EgressSited", "ResizeHalf"]
+           "iter_yuv422", "EgressYuv422", "UnpackYuv422", "iter_deep444", "EgressDeep444", "UnpackDeep444", "UnpackSited", "EgressSited", "ResizeHalf", "Resample"]

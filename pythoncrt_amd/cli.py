@@ -85,7 +85,7 @@ import time
 
 import numpy as np
 
-from . import formats, sited
+from . import formats, sited, tables
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -174,6 +174,9 @@ def add_output_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
                    help="width of the frames written, with --deliver-height: the frames are rendered at --width x --height and resized on the GPU behind "
                         "the chain (a 4K render written as 1080p); 0 (default) = as rendered")
     p.add_argument("--deliver-height", type=int, default=0, help="height of the frames written (see --deliver-width); 0 (default) = as rendered")
+    p.add_argument("--deliver-filter", type=str, default="bilinear", choices=list(tables.RESAMPLE_FILTERS),
+                   help="filter of the --deliver-width / --deliver-height resize: Pillow's BILINEAR (default) or another of its five, e.g. lanczos or "
+                        "bicubic for a 4K render written as 1080p; needs a delivery size other than the render size")
     return p
 
 
@@ -189,6 +192,13 @@ def deliver_size_from_args(a):
     return None if (dh, dw) == (int(a.height), int(a.width)) else (dh, dw)
 
 
+def check_filter_flags(a, deliver) -> None:
+    """--deliver-filter other than bilinear needs a delivery resize to apply to (`deliver` is deliver_size_from_args(a))."""
+    if getattr(a, "deliver_filter", "bilinear") != "bilinear" and deliver is None:
+        raise SystemExit(f"--deliver-filter {a.deliver_filter} without --deliver-width / --deliver-height other than the render size: "
+                         "there is no delivery resize to filter")
+
+
 def add_input_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     """The input-format flags of `main` (not in the reference, whose reader pipe is always `-pix_fmt rgb24`, ref:489-502).  Kept out of
     `build_parser`, as `add_output_flags` is."""
@@ -202,6 +212,10 @@ def add_input_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--in-chroma", type=str, default="replicate", choices=["replicate", "left", "center"],
                    help="4:2:0 / 4:2:2 input: replicate each chroma sample over its pixels (default), or interpolate chroma at its siting on the GPU: "
                         "left (MPEG-2 / H.264 / HEVC; ffprobe's chroma_location=left or nothing) or center (JPEG-family sources)")
+    p.add_argument("--in-filter", type=str, default="bilinear", choices=list(tables.RESAMPLE_FILTERS),
+                   help="filter of the resize that brings a source of another size to --width x --height (process_frames(in_filter=)): Pillow's "
+                        "BILINEAR (default) or another of its five; a raw input file is read at --width x --height, so nothing is resized in "
+                        "front of the chain here")
     return p
 
 
@@ -914,6 +928,10 @@ def main_sharded(a, rank: int, world: int) -> int:
         # every rank writes its chunks at offsets of its own: those, and the downloads behind them, are at render size here
         raise SystemExit("--deliver-width / --deliver-height are not supported by the sharded CLI (one process per GPU writes rgb24 at render size); "
                          "run one process, or scale behind it")
+    for flag, value in (("--in-filter", getattr(a, "in_filter", "bilinear")), ("--deliver-filter", getattr(a, "deliver_filter", "bilinear"))):
+        if value != "bilinear":
+            raise SystemExit(f"{flag} {value} is not supported by the sharded CLI (one process per GPU reads and writes rgb24 at render size: "
+                             "nothing is resized); run one process, or scale outside it")
     if getattr(a, "out_pix_fmt", "rgb24") != "rgb24":
         # every rank writes its chunks at offsets of its own: those, and the downloads behind them, are rgb24-sized here
         raise SystemExit(f"--out-pix-fmt {a.out_pix_fmt} is not supported by the sharded CLI (one process per GPU writes rgb24 only); "
@@ -1062,6 +1080,7 @@ def main(argv=None) -> int:
         if a.gui or not a.input or a.width <= 0 or a.height <= 0:
             raise SystemExit("pass --input, --width and --height")
         return main_sharded(a, int(_os.environ.get("RANK", "0")), int(_os.environ.get("WORLD_SIZE", "1")))
+    check_filter_flags(a, deliver)
     if a.gui or not a.input:
         raise SystemExit("the GUI is not part of this path; pass --input (raw rgb24 / yuv420p / nv12 / yuv422p / yuyv422 / uyvy422 / yuv420p10le / p010le / yuv444p10le / gbrp10le / x2rgb10le file or '-')")
     if a.width <= 0 or a.height <= 0:
@@ -1098,7 +1117,10 @@ def main(argv=None) -> int:
     dh, dw = deliver if deliver is not None else (h, w)
     resize_out = None
     if deliver is not None:
-        if deep:
+        if a.deliver_filter != "bilinear":                          # Resample (include/crtfx_resample.h): uint8 or half frames, signed taps
+            from .resample import Resample
+            resize_out = Resample(dev, (h, w), (dh, dw), filter=a.deliver_filter, dtype=pix)
+        elif deep:
             from .resize16 import ResizeHalf
             resize_out = ResizeHalf(dev, (h, w), (dh, dw))
         else:

@@ -20,7 +20,7 @@ from typing import Callable, Iterable, Optional, Tuple
 
 import numpy as np
 
-from . import formats, sited
+from . import formats, sited, tables
 
 # process_video keywords that belong to its container / codec plumbing (out of scope): accepted so that a caller can forward its
 # own keyword dictionary unchanged, and ignored
@@ -108,7 +108,8 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                    batch: int = 16, noise_seed: Optional[int] = None, device=None, resize_on: str = "device",
                    out_pix_fmt: str = "rgb24", out_matrix: str = "bt601", out_range: str = "tv",
                    in_pix_fmt: str = "rgb24", in_matrix: str = "bt601", in_range: str = "tv", in_size: Optional[Tuple[int, int]] = None,
-                   in_chroma: str = "replicate", out_chroma: str = "center", deliver_size: Optional[Tuple[int, int]] = None, **io_keywords) -> int:
+                   in_chroma: str = "replicate", out_chroma: str = "center", deliver_size: Optional[Tuple[int, int]] = None,
+                   in_filter: str = "bilinear", deliver_filter: str = "bilinear", **io_keywords) -> int:
     """Render every frame of `frame_iter` (H x W x 3 uint8 RGB arrays) and hand the finished uint8 frames to `write_frame` in order.
     Effect keywords: the names, meaning and defaults of process_video / the CLI (ref:864-911, :1155-1206); the caller applies the clamps of
     ref:1225-1266 as the reference's `main` does (`pythoncrt_amd.cli.settings_from_args` restates them).  Returns the number of frames written.
@@ -165,6 +166,13 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     frame_bytes(dh, dw) bytes).  `None` (default) and the render size itself are the path as it was: no resize plan is created.  Refused
     with ValueError before a device is touched: a value that is not a pair of integers, a size < 1 or > 32767.  (`in_size` for a 10-bit
     input stays refused: the source side of the half chain has no resize.)
+    `in_filter` / `deliver_filter` name the filter of those two resizes, one of tables.RESAMPLE_FILTERS ("box", "bilinear", "hamming",
+    "bicubic", "lanczos": Pillow's five).  "bilinear" (default) is the path as it was: IngestResize / ResizeHalf, their plan strings and
+    bytes, and no Resample plan is created.  With another name Resample (include/crtfx_resample.h) stands where IngestResize stands for an
+    off-size rgb24, 4:2:0 or 4:2:2 source, and where IngestResize or ResizeHalf stands behind the chain; uint8 frames come out as
+    `Image.resize(size, filter)` gives them, and `resize_on="host"` hands `in_filter` to Pillow itself (the same bytes).  Refused with
+    ValueError before a device is touched: an unknown name, and a `deliver_filter` other than "bilinear" without a `deliver_size` that
+    differs from the render size (there is nothing to filter).
     If `frame_iter` or `write_frame` raises, the GPU work already queued is drained (device synchronize) before the exception leaves this
     function, so that the staging buffers are not freed under a running copy."""
     import os
@@ -201,6 +209,12 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     if in_pix_fmt != "rgb24" and resize_on == "host":
         raise ValueError(f"resize_on='host' cannot be combined with in_pix_fmt={in_pix_fmt!r}: there is no host RGB frame to hand to Pillow")
     deliver = parse_deliver_size(deliver_size, int(out_h), int(out_w))         # None: delivered as rendered
+    for name, value in (("in_filter", in_filter), ("deliver_filter", deliver_filter)):
+        if value not in tables.RESAMPLE_FILTERS:
+            raise ValueError(f"{name} must be one of {', '.join(tables.RESAMPLE_FILTERS)}, got {value!r}")
+    if deliver_filter != "bilinear" and deliver is None:
+        raise ValueError(f"deliver_filter={deliver_filter!r} without a deliver_size that differs from the render size: there is no delivery "
+                         "resize to filter")
     if not torch.cuda.is_available():
         raise RuntimeError("no ROCm device visible; pythoncrt_amd has no CPU fallback")
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -238,7 +252,10 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     out_shape = (B, dh, dw, 3) if egress is None else (B, egress.frame_bytes)  # what is downloaded and handed to the writer
     resize_out = None
     if deliver is not None:                                                    # the finished frames at the delivery size, between the chain and the egress plan
-        if deep:
+        if deliver_filter != "bilinear":
+            from .resample import Resample
+            resize_out = Resample(dev, (h, w), (dh, dw), filter=deliver_filter, dtype=pix)
+        elif deep:
             from .resize16 import ResizeHalf
             resize_out = ResizeHalf(dev, (h, w), (dh, dw))
         else:
@@ -259,6 +276,14 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     state, index, written, k = None, 0, 0, 0
     pending = None                   # (slot, frames, download event) of the batch whose frames are still to be written
 
+    def resize_in(src_hw):
+        """The plan that brings uint8 RGB frames of a source size to the render size: IngestResize, or Resample under another in_filter."""
+        if in_filter != "bilinear":
+            from .resample import Resample
+            return Resample(dev, src_hw, (h, w), filter=in_filter, dtype=torch.uint8)
+        from .ingest import IngestResize
+        return IngestResize(dev, src_hw, (h, w))
+
     MAX_SOURCES = 4                  # source sizes whose staging buffers and ingest plan are kept
     sources = {}                     # (src_h, src_w) -> _Source, in order of last use
     carry = None                     # a frame already taken from the iterator that starts the next batch (its source size differs)
@@ -266,8 +291,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     class _Source:
         """Staging of one off-size source: pinned and device slots of ITS size, the plan that resizes them into dev_in[d]."""
         def __init__(self, sh, sw):
-            from .ingest import IngestResize
-            self.plan = IngestResize(dev, (sh, sw), (h, w))
+            self.plan = resize_in((sh, sw))
             self.pin = [torch.empty((B, sh, sw, 3), dtype=torch.uint8).pin_memory() for _ in range(NS)]
             self.dev = [torch.empty((B, sh, sw, 3), dtype=torch.uint8, device=dev) for _ in range(NS)]
             self.np = [t.numpy() for t in self.pin]
@@ -293,8 +317,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
             assert self.nbytes == yuv_bytes
             self.resize, self.rgb = None, None
             if yuv_hw != (h, w):
-                from .ingest import IngestResize
-                self.resize = IngestResize(dev, yuv_hw, (h, w))
+                self.resize = resize_in(yuv_hw)
                 self.rgb = [torch.empty((B,) + yuv_hw + (3,), dtype=torch.uint8, device=dev) for _ in range(NS)]
             self.pin = [torch.empty((B, self.nbytes), dtype=torch.uint8).pin_memory() for _ in range(NS)]
             self.dev = [torch.empty((B, self.nbytes), dtype=torch.uint8, device=dev) for _ in range(NS)]
@@ -335,7 +358,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
             if resize_on == "device":
                 return a, (int(a.shape[0]), int(a.shape[1]))
             from PIL import Image
-            a = np.asarray(Image.fromarray(np.ascontiguousarray(a, dtype=np.uint8)).resize((w, h), Image.BILINEAR))
+            a = np.asarray(Image.fromarray(np.ascontiguousarray(a, dtype=np.uint8)).resize((w, h), getattr(Image, in_filter.upper())))
         return a, None
 
     def drain(p):

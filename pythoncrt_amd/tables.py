@@ -280,6 +280,79 @@ def pil_resample_axis(n_in: int, n_out: int):
     return np.ascontiguousarray(xmin.astype(np.int32)), np.ascontiguousarray(count.astype(np.int32)), np.ascontiguousarray(k)
 
 
+RESAMPLE_FILTERS = ("box", "bilinear", "hamming", "bicubic", "lanczos")      # Pillow's Image.BOX / BILINEAR / HAMMING / BICUBIC / LANCZOS
+
+
+def _sinc(x):
+    with np.errstate(divide="ignore", invalid="ignore"):
+        px = x * np.pi
+        v = np.sin(px) / px
+    return np.where(x == 0.0, 1.0, v)
+
+
+def _filter_box(x):
+    return np.where((x > -0.5) & (x <= 0.5), 1.0, 0.0)
+
+
+def _filter_bilinear(x):
+    a = np.abs(x)
+    return np.where(a < 1.0, 1.0 - a, 0.0)
+
+
+def _filter_hamming(x):
+    a = np.abs(x)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        px = a * np.pi
+        v = np.sin(px) / px * (0.54 + 0.46 * np.cos(px))
+    return np.where(a == 0.0, 1.0, np.where(a >= 1.0, 0.0, v))
+
+
+def _filter_bicubic(x):
+    A = -0.5                                                      # Keys: the `a` of Pillow's bicubic_filter
+    a = np.abs(x)
+    return np.where(a < 1.0, ((A + 2.0) * a - (A + 3.0)) * a * a + 1, np.where(a < 2.0, (((a - 5) * a + 8) * a - 4) * A, 0.0))
+
+
+def _filter_lanczos(x):
+    return np.where((x >= -3.0) & (x < 3.0), _sinc(x) * _sinc(x / 3), 0.0)
+
+
+# name -> (the filter of Pillow's Resample.c as a float64 expression, its support)
+_FILTERS = {"box": (_filter_box, 0.5), "bilinear": (_filter_bilinear, 1.0), "hamming": (_filter_hamming, 1.0),
+            "bicubic": (_filter_bicubic, 2.0), "lanczos": (_filter_lanczos, 3.0)}
+
+
+def pil_filter_axis(n_in: int, n_out: int, filter: str):
+    """One axis of Pillow's 8-bit resampler for any of RESAMPLE_FILTERS (`Image.resize(..., Image.LANCZOS)` and its kin; precompute_coeffs +
+    normalize_coeffs_8bpc of src/libImaging/Resample.c) as SIGNED integer tables for crtfx_resample_create (include/crtfx_resample.h):
+    (xmin int32[n_out], count int32[n_out], k int32[n_out, ksize]).  Output sample xx of a pass is
+    clamp((2**21 + sum(k[xx, t] * sample[xmin[xx] + t] for t < count[xx])) >> 22, 0, top), the shift arithmetic.  The window is that of
+    pil_resample_axis with the filter's support (0.5 / 1 / 1 / 2 / 3) in place of 1; a weight rounds away from zero by a half and truncates,
+    as the C cast does.  Float64 throughout in Pillow's order of operations; for "bilinear" the arrays are pil_resample_axis's."""
+    if filter not in _FILTERS:
+        raise ValueError(f"filter must be one of {', '.join(RESAMPLE_FILTERS)}, got {filter!r}")
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"pil_filter_axis({n_in}, {n_out})")
+    f, filter_support = _FILTERS[filter]
+    scale = np.float64(n_in) / np.float64(n_out)
+    fs = max(scale, np.float64(1.0))
+    support = np.float64(filter_support) * fs
+    ksize = int(np.ceil(support)) * 2 + 1
+    ss = np.float64(1.0) / fs
+    center = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)                 # astype truncates as the C cast does
+    count = np.minimum((center + support + 0.5).astype(np.int64), n_in) - xmin
+    x = np.arange(ksize, dtype=np.int64)[None, :]
+    w = f(((x + xmin[:, None]).astype(np.float64) - center[:, None] + 0.5) * ss)
+    w = np.where(x < count[:, None], w, 0.0)
+    ww = np.add.accumulate(w, axis=1)[:, -1:]                     # sequential, in tap order (the zeros behind `count` add nothing)
+    w = np.divide(w, ww, out=w.copy(), where=ww != 0.0)
+    p = w * np.float64(1 << 22)                                   # PRECISION_BITS = 32 - 8 - 2
+    k = np.where(p < 0.0, -0.5 + p, 0.5 + p).astype(np.int32)
+    return np.ascontiguousarray(xmin.astype(np.int32)), np.ascontiguousarray(count.astype(np.int32)), np.ascontiguousarray(k)
+
+
 def ptr(a) -> int:
     return 0 if a is None else a.ctypes.data
 
