@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("CRTFX_LIB") or os.path.join(_HERE, "libcrtfx.so")   #
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = [os.path.join(CSRC, f) for f in ("crtfx.hip", "crtfx_rr.hip", "crtfx_kernels.hip.h", "crtfx_common.hip.h", "crtfx_blur.hip.h", "crtfx_point.hip.h",
                                                 "crtfx_phosphor.hip.h", "crtfx_phosphor_ct.hip.h", "crtfx_warp.hip.h", "crtfx_internal.h", "crtfx_ingest.hip",
-                                                "crtfx_egress.hip", "crtfx_unpack.hip", "crtfx_deep.hip", "crtfx_422.hip", "crtfx_444.hip", "crtfx_sited.hip", "crtfx_egress_sited.hip", "crtfx_resize16.hip", "crtfx_resample.hip", "crtfx_stage_host.h")] + \
+                                                "crtfx_egress.hip", "crtfx_unpack.hip", "crtfx_deep.hip", "crtfx_422.hip", "crtfx_444.hip", "crtfx_sited.hip", "crtfx_egress_sited.hip", "crtfx_resize16.hip", "crtfx_resample.hip", "crtfx_stage_host.h", "crtfx_resize_host.h")] + \
           [os.path.join(ROOT, "include", f) for f in ("crtfx.h", "crtfx_ingest.h", "crtfx_egress.h", "crtfx_unpack.h", "crtfx_deep.h", "crtfx_422.h", "crtfx_444.h", "crtfx_sited.h", "crtfx_egress_sited.h", "crtfx_resize16.h", "crtfx_resample.h")]
 STAGE_UNITS = ("crtfx_ingest", "crtfx_egress", "crtfx_unpack", "crtfx_deep", "crtfx_422", "crtfx_444", "crtfx_sited", "crtfx_egress_sited", "crtfx_resize16", "crtfx_resample")   # one object file each, beside crtfx.hip / crtfx_rr.hip
 RR_RADII = tuple(range(1, 31))      # one register-window build per radius up to 30 (crtfx_internal.h); larger radii: the split path
@@ -90,16 +90,21 @@ SYMBOLS = {
     "crtfx_host_blur_row": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int]),
 }
 
+def resize_symbols(*families):
+    """The six entry points of each crtfx_<family>_* family of resize stages (include/crtfx_ingest.h spells them out; pythoncrt_amd/_stage.py
+    is their one caller)."""
+    return {f"crtfx_{fam}_{name}": sig for fam in families for name, sig in (
+        ("create", (ctypes.c_int, [ctypes.c_int] * 6 + [_vp, _vp, _vp, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int, ctypes.POINTER(_vp)])),
+        ("destroy", (ctypes.c_int, [_vp])),
+        ("last_error", (ctypes.c_char_p, [_vp])),
+        ("run", (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp])),
+        ("set_option", (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int])),
+        ("last_plan", (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t])))}
+
+
 # ... and every symbol include/crtfx_ingest.h declares (the ingest stage: a handle of its own, pythoncrt_amd/ingest.py)
 INGEST_OPT_FORCE_GENERAL = 1
-INGEST_SYMBOLS = {
-    "crtfx_ingest_create": (ctypes.c_int, [ctypes.c_int] * 6 + [_vp, _vp, _vp, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int, ctypes.POINTER(_vp)]),
-    "crtfx_ingest_destroy": (ctypes.c_int, [_vp]),
-    "crtfx_ingest_last_error": (ctypes.c_char_p, [_vp]),
-    "crtfx_ingest_run": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
-    "crtfx_ingest_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
-    "crtfx_ingest_last_plan": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t]),
-}
+INGEST_SYMBOLS = resize_symbols("ingest")
 
 
 def stage_symbols(*families):
@@ -157,26 +162,12 @@ EGRESS_SITED_SYMBOLS = stage_symbols("egress_sited")
 # ... and every symbol include/crtfx_resize16.h declares (the half resampler: a handle of its own, pythoncrt_amd/resize16.py; the shape of the
 # ingest stage's table)
 RESIZE16_OPT_FORCE_GENERAL = 1
-RESIZE16_SYMBOLS = {
-    "crtfx_resize16_create": (ctypes.c_int, [ctypes.c_int] * 6 + [_vp, _vp, _vp, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int, ctypes.POINTER(_vp)]),
-    "crtfx_resize16_destroy": (ctypes.c_int, [_vp]),
-    "crtfx_resize16_last_error": (ctypes.c_char_p, [_vp]),
-    "crtfx_resize16_run": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
-    "crtfx_resize16_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
-    "crtfx_resize16_last_plan": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t]),
-}
+RESIZE16_SYMBOLS = resize_symbols("resize16")
 
 # ... and every symbol include/crtfx_resample.h declares (the filtered resampler, uint8 and half: a handle of its own, pythoncrt_amd/resample.py;
 # the shape of the ingest stage's table)
 RESAMPLE_OPT_FORCE_GENERAL, RESAMPLE_OPT_ACC64 = 1, 2
-RESAMPLE_SYMBOLS = {
-    "crtfx_resample_create": (ctypes.c_int, [ctypes.c_int] * 6 + [_vp, _vp, _vp, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int, ctypes.POINTER(_vp)]),
-    "crtfx_resample_destroy": (ctypes.c_int, [_vp]),
-    "crtfx_resample_last_error": (ctypes.c_char_p, [_vp]),
-    "crtfx_resample_run": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
-    "crtfx_resample_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
-    "crtfx_resample_last_plan": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t]),
-}
+RESAMPLE_SYMBOLS = resize_symbols("resample")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC"]
 

@@ -1117,15 +1117,8 @@ def main(argv=None) -> int:
     dh, dw = deliver if deliver is not None else (h, w)
     resize_out = None
     if deliver is not None:
-        if a.deliver_filter != "bilinear":                          # Resample (include/crtfx_resample.h): uint8 or half frames, signed taps
-            from .resample import Resample
-            resize_out = Resample(dev, (h, w), (dh, dw), filter=a.deliver_filter, dtype=pix)
-        elif deep:
-            from .resize16 import ResizeHalf
-            resize_out = ResizeHalf(dev, (h, w), (dh, dw))
-        else:
-            from .ingest import IngestResize
-            resize_out = IngestResize(dev, (h, w), (dh, dw))
+        from ._stage import resize_plan                              # Resample (include/crtfx_resample.h) under another filter: signed taps
+        resize_out = resize_plan(dev, (h, w), (dh, dw), a.deliver_filter, pix)
     # --out-pix-fmt yuv420p / nv12 / yuv422p / yuyv422 / uyvy422: the chain's frames are converted on the device behind it (EgressYuv) and everything downstream — the device
     # and pinned output slots, the download, the output file's offsets and size — is in frames of out_bytes instead of frame_bytes
     egress = None

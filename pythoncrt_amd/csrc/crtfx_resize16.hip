@@ -1,15 +1,13 @@
 // crtfx_resize16.hip — the half resampler of libcrtfx.so (include/crtfx_resize16.h): Pillow's 8-bit BILINEAR resize on the quarter-code scale,
 // h x w x 3 half RGB frames on the device.  A translation unit of its own: it shares no kernel, table or handle with the effect chain or with
-// the ingest stage whose structure it follows; of the format stages' host skeleton (crtfx_stage_host.h, host templates only) it takes the
-// device guard and the error helper.
+// the ingest stage whose structure it follows.  Here are its kernels, its handle and what the resize stages' host skeleton
+// (crtfx_resize_host.h, host templates only) asks of a unit; create, run and the other entry points are that skeleton's.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
-#include <cstring>
-#include <vector>
 
 #include "crtfx_resize16.h"
-#include "crtfx_stage_host.h"
+#include "crtfx_resize_host.h"
 
 namespace crtfx_resize16_impl {
 
@@ -17,8 +15,6 @@ constexpr int BLOCK = 256;
 constexpr int PREC = 22;                       // Pillow's PRECISION_BITS (32 - 8 - 2)
 constexpr unsigned HALF = 1u << (PREC - 1);
 constexpr unsigned QMAX = 1020;                // the largest quarter code (255.0 on the half scale)
-constexpr int LDS_BUDGET = 40960;              // four blocks per CU (160 KB of LDS)
-constexpr size_t SCRATCH_BYTES = 64u << 20;    // general path: frames per group = what fits this much horizontal-pass scratch (at least one, at most 64)
 
 struct Axis { const int32_t* min; const int32_t* count; const int32_t* k; int ksize; };
 
@@ -194,207 +190,96 @@ __global__ __launch_bounds__(BLOCK) void k_resize16_v(const uint16_t* tmp, uint1
 }  // namespace crtfx_resize16_impl
 
 using namespace crtfx_resize16_impl;
-using namespace crtfx_stage;       // DeviceGuard, fail and create_err; the plan, create and run are this stage's own
 
-struct crtfx_resize16 {
-    int device = 0;
-    int sh = 0, sw = 0, dh = 0, dw = 0;
-    int32_t* tables = nullptr;          // one device allocation: x min | x count | x k | y min | y count | y k
-    Axis x{}, y{};
-    bool fused_fits = false;            // some tile shape meets the LDS budget
-    Args fused{};                       // its launch constants (frame pointers filled per run)
-    int lds_bytes = 0;
-    uint16_t* scratch = nullptr;        // general path: scratch_frames x sh x dw x 3
-    int scratch_frames = 0;
-    bool force_general = false;
-    char plan[128] = "";
-    std::string err;
-};
+struct crtfx_resize16 : crtfx_resize::Plan<Axis, Args> {};
 
 namespace {
 
-int log2_ceil(int v) { int s = 0; while ((1 << s) < v) ++s; return s; }
+using crtfx_resize::fail;
 
-// the rules crtfx_ingest.h states for a table, and the accumulator bound of crtfx_resize16.h; the kernels' bounds rest on them
-const char* check_axis(const int32_t* mn, const int32_t* cnt, const int32_t* k, int ksize, int n_in, int n_out) {
-    for (int i = 0; i < n_out; ++i) {
-        if (mn[i] < 0 || cnt[i] < 1 || cnt[i] > ksize || mn[i] > n_in - cnt[i]) return "a tap window leaves the source (min >= 0, 1 <= count <= ksize, min + count <= n_in)";
-        if (i && (mn[i] < mn[i - 1] || mn[i] + cnt[i] < mn[i - 1] + cnt[i - 1])) return "min and min + count must be non-decreasing";
+// what crtfx_resize_host.h asks of a unit
+struct Unit {
+    using H = crtfx_resize16;
+    static constexpr int force_option = CRTFX_RESIZE16_OPT_FORCE_GENERAL;
+    static const char* name() { return "resize16"; }
+    static int bps(int) { return 2; }
+
+    static int check_pix_fmt(int pix_fmt) {
+        if (pix_fmt == CRTFX_PIX_U8) return fail<H>(nullptr, CRTFX_E_UNSUPPORTED, "only half RGB frames are resized here (uint8 frames have crtfx_ingest_*)");
+        if (pix_fmt != CRTFX_PIX_F16) return fail<H>(nullptr, CRTFX_E_INVALID, "unknown pixel format %d", pix_fmt);
+        return CRTFX_OK;
+    }
+
+    // the coefficient rule of crtfx_ingest.h, and the accumulator bound of crtfx_resize16.h
+    static const char* check_row(const int32_t* k, int cnt) {
         unsigned long long sum = 0;
-        for (int t = 0; t < cnt[i]; ++t) {
-            if (k[(size_t)i * ksize + t] < 0 || k[(size_t)i * ksize + t] >= (1 << 24)) return "a coefficient is outside [0, 2^24)";
-            sum += (unsigned long long)k[(size_t)i * ksize + t];
+        for (int t = 0; t < cnt; ++t) {
+            if (k[t] < 0 || k[t] >= (1 << 24)) return "a coefficient is outside [0, 2^24)";
+            sum += (unsigned long long)k[t];
         }
         if (sum * QMAX + HALF >= (1ull << 32)) return "a row's accumulator could wrap (sum(k) * 1020 + 2^21 >= 2^32)";
+        return nullptr;
     }
-    return nullptr;
-}
 
-// largest source extent (taps of the first .. last output index) over the tiles of `tile` output indices
-int max_extent(const int32_t* mn, const int32_t* cnt, int n_out, int tile) {
-    int m = 0;
-    for (int o = 0; o < n_out; o += tile) {
-        const int last = (o + tile < n_out ? o + tile : n_out) - 1;
-        const int e = mn[last] + cnt[last] - mn[o];
-        if (e > m) m = e;
+    static void lds_rows(const H*, long long nc, int cols, long long* P, long long* HP, int* v_items) {
+        *P = (6 * nc + 2 + 3) & ~3LL;
+        *HP = (6LL * cols + 3) & ~3LL;
+        *v_items = (3 * cols) / 2 + 2;
     }
-    return m;
-}
 
-void plan_fused(crtfx_resize16* p, const int32_t* xmin, const int32_t* xcnt, const int32_t* ymin, const int32_t* ycnt) {
-    static const int shapes[][2] = {{32, 128}, {32, 64}, {16, 128}, {16, 64}, {8, 64}, {8, 32}, {4, 32}};
-    for (const auto& s : shapes) {
-        const int TH = s[0], TW = s[1];
-        const int rows = TH < p->dh ? TH : p->dh, cols = TW < p->dw ? TW : p->dw;
-        const long long nr = max_extent(ymin, ycnt, p->dh, TH), nc = max_extent(xmin, xcnt, p->dw, TW);
-        const long long P = (6 * nc + 2 + 3) & ~3LL, HP = (6LL * cols + 3) & ~3LL;
-        const long long tab = 4LL * (2 * cols + (long long)cols * p->x.ksize + 2 * rows + (long long)rows * p->y.ksize);
-        const long long total = tab + nr * (P + HP);
-        if (total > LDS_BUDGET) continue;
-        Args& a = p->fused;
-        a = Args{};
-        a.sh = p->sh; a.sw = p->sw; a.dh = p->dh; a.dw = p->dw;
-        a.TH = rows; a.TW = cols; a.P = (int)P; a.HP = (int)HP; a.nr_max = (int)nr;
-        a.sh_stage = log2_ceil((int)(P >> 2));
-        a.sh_h = log2_ceil(cols);
-        a.sh_v = log2_ceil((3 * cols) / 2 + 2);
-        p->lds_bytes = (int)total;
-        p->fused_fits = true;
-        return;
+    static void note_plan(H* p, int frames) {
+        if (p->fused_fits && !p->force_general)
+            snprintf(p->plan, sizeof p->plan, "resize16=k_resize16_fused<rows=%d,cols=%d>;lds=%d;frames=%d", p->fused.TH, p->fused.TW, p->lds_bytes, frames);
+        else
+            snprintf(p->plan, sizeof p->plan, "resize16=k_resize16_h+k_resize16_v;frames=%d", frames);
     }
-}
 
-void note_plan(crtfx_resize16* p, int frames) {
-    if (p->fused_fits && !p->force_general)
-        snprintf(p->plan, sizeof p->plan, "resize16=k_resize16_fused<rows=%d,cols=%d>;lds=%d;frames=%d", p->fused.TH, p->fused.TW, p->lds_bytes, frames);
-    else
-        snprintf(p->plan, sizeof p->plan, "resize16=k_resize16_h+k_resize16_v;frames=%d", frames);
-}
+    static int check_alignment(H* p, const void* src, size_t src_stride_bytes, const void* dst, size_t dst_stride_bytes) {
+        if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | src_stride_bytes | dst_stride_bytes) & 1u)
+            return fail(p, CRTFX_E_INVALID, "frame bases and strides must be even (16-bit elements)");
+        return CRTFX_OK;
+    }
+
+    static void launch(H* p, bool fused, const unsigned char* src_bytes, size_t src_stride_bytes, unsigned char* dst_bytes, size_t dst_stride_bytes, int g,
+                       hipStream_t st) {
+        const uint16_t* src = reinterpret_cast<const uint16_t*>(src_bytes);
+        uint16_t* dst = reinterpret_cast<uint16_t*>(dst_bytes);
+        uint16_t* scratch = static_cast<uint16_t*>(p->scratch);
+        const size_t ss = src_stride_bytes / 2, ds = dst_stride_bytes / 2;           // the kernels' strides are in 16-bit elements
+        if (fused) {
+            Args a = p->fused;
+            a.x = p->x; a.y = p->y;
+            a.src = src; a.src_stride = ss;
+            a.dst = dst; a.dst_stride = ds;
+            dim3 grid((p->dw + a.TW - 1) / a.TW, (p->dh + a.TH - 1) / a.TH, g);
+            hipLaunchKernelGGL(k_resize16_fused, grid, dim3(BLOCK), (size_t)p->lds_bytes, st, a);
+        } else {
+            hipLaunchKernelGGL(k_resize16_h, dim3((p->dw + BLOCK - 1) / BLOCK, p->sh, g), dim3(BLOCK), 0, st, src, ss, scratch, p->sh, p->sw, p->dw, p->x);
+            hipLaunchKernelGGL(k_resize16_v, dim3((p->dw * 3 + BLOCK - 1) / BLOCK, p->dh, g), dim3(BLOCK), 0, st, scratch, dst, ds, p->sh, p->dw, p->y);
+        }
+    }
+};
 
 }  // namespace
 
 extern "C" {
 
-const char* crtfx_resize16_last_error(const crtfx_resize16* p) { return p ? p->err.c_str() : create_err<crtfx_resize16>().c_str(); }
+const char* crtfx_resize16_last_error(const crtfx_resize16* p) { return p ? p->err.c_str() : crtfx_resize::create_err<crtfx_resize16>().c_str(); }
 
 int crtfx_resize16_create(int device, int src_h, int src_w, int dst_h, int dst_w, int pix_fmt,
                           const int32_t* x_min, const int32_t* x_count, const int32_t* x_k, int x_ksize,
                           const int32_t* y_min, const int32_t* y_count, const int32_t* y_k, int y_ksize, crtfx_resize16** out_plan) {
-    create_err<crtfx_resize16>().clear();
-    if (!out_plan) return fail<crtfx_resize16>(nullptr, CRTFX_E_INVALID, "out_plan is null");
-    *out_plan = nullptr;
-    if (pix_fmt == CRTFX_PIX_U8) return fail<crtfx_resize16>(nullptr, CRTFX_E_UNSUPPORTED, "only half RGB frames are resized here (uint8 frames have crtfx_ingest_*)");
-    if (pix_fmt != CRTFX_PIX_F16) return fail<crtfx_resize16>(nullptr, CRTFX_E_INVALID, "unknown pixel format %d", pix_fmt);
-    if (src_h < 1 || src_w < 1 || dst_h < 1 || dst_w < 1 || src_h > 32767 || src_w > 32767 || dst_h > 32767 || dst_w > 32767)
-        return fail<crtfx_resize16>(nullptr, CRTFX_E_INVALID, "sizes %dx%d -> %dx%d outside 1..32767", src_h, src_w, dst_h, dst_w);
-    if (!x_min || !x_count || !x_k || !y_min || !y_count || !y_k) return fail<crtfx_resize16>(nullptr, CRTFX_E_INVALID, "a table is null");
-    if (x_ksize < 1 || y_ksize < 1) return fail<crtfx_resize16>(nullptr, CRTFX_E_INVALID, "ksize %d / %d < 1", x_ksize, y_ksize);
-    if (const char* why = check_axis(x_min, x_count, x_k, x_ksize, src_w, dst_w)) return fail<crtfx_resize16>(nullptr, CRTFX_E_INVALID, "x tables: %s", why);
-    if (const char* why = check_axis(y_min, y_count, y_k, y_ksize, src_h, dst_h)) return fail<crtfx_resize16>(nullptr, CRTFX_E_INVALID, "y tables: %s", why);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail<crtfx_resize16>(nullptr, CRTFX_E_HIP, "no HIP device %d", device);
-    DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return fail<crtfx_resize16>(nullptr, CRTFX_E_HIP, "hipSetDevice(%d): %s", device, hipGetErrorString(guard.err));
-    crtfx_resize16* p = new (std::nothrow) crtfx_resize16();
-    if (!p) return fail<crtfx_resize16>(nullptr, CRTFX_E_NOMEM, "out of host memory");
-    p->device = device; p->sh = src_h; p->sw = src_w; p->dh = dst_h; p->dw = dst_w;
-    p->x.ksize = x_ksize; p->y.ksize = y_ksize;
-    plan_fused(p, x_min, x_count, y_min, y_count);
-
-    std::vector<int32_t> host;
-    host.reserve((size_t)dst_w * (2 + x_ksize) + (size_t)dst_h * (2 + y_ksize));
-    host.insert(host.end(), x_min, x_min + dst_w);
-    host.insert(host.end(), x_count, x_count + dst_w);
-    host.insert(host.end(), x_k, x_k + (size_t)dst_w * x_ksize);
-    host.insert(host.end(), y_min, y_min + dst_h);
-    host.insert(host.end(), y_count, y_count + dst_h);
-    host.insert(host.end(), y_k, y_k + (size_t)dst_h * y_ksize);
-    const size_t frame_tmp = (size_t)src_h * dst_w * 3 * sizeof(uint16_t);
-    p->scratch_frames = p->fused_fits ? 1 : (int)(SCRATCH_BYTES / frame_tmp);      // behind a fused plan the general path is an A/B switch only
-    if (p->scratch_frames < 1) p->scratch_frames = 1;
-    if (p->scratch_frames > 64) p->scratch_frames = 64;
-    hipError_t e = hipMalloc((void**)&p->tables, host.size() * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&p->scratch, frame_tmp * p->scratch_frames);
-    if (e == hipSuccess) e = hipMemcpy(p->tables, host.data(), host.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        const int code = e == hipErrorOutOfMemory ? CRTFX_E_NOMEM : CRTFX_E_HIP;
-        fail<crtfx_resize16>(nullptr, code, "crtfx_resize16_create: %s", hipGetErrorString(e));
-        if (p->tables) (void)hipFree(p->tables);
-        if (p->scratch) (void)hipFree(p->scratch);
-        delete p;
-        return code;
-    }
-    int32_t* t = p->tables;
-    p->x.min = t; t += dst_w; p->x.count = t; t += dst_w; p->x.k = t; t += (size_t)dst_w * x_ksize; p->x.ksize = x_ksize;
-    p->y.min = t; t += dst_h; p->y.count = t; t += dst_h; p->y.k = t; p->y.ksize = y_ksize;
-    note_plan(p, 0);
-    *out_plan = p;
-    return CRTFX_OK;
+    return crtfx_resize::create<Unit>(device, src_h, src_w, dst_h, dst_w, pix_fmt, x_min, x_count, x_k, x_ksize, y_min, y_count, y_k, y_ksize, out_plan);
 }
 
-int crtfx_resize16_destroy(crtfx_resize16* p) {
-    if (!p) return CRTFX_OK;
-    DeviceGuard guard(p->device);
-    (void)hipDeviceSynchronize();
-    if (p->tables) (void)hipFree(p->tables);
-    if (p->scratch) (void)hipFree(p->scratch);
-    delete p;
-    return CRTFX_OK;
-}
+int crtfx_resize16_destroy(crtfx_resize16* p) { return crtfx_resize::destroy(p); }
 
-int crtfx_resize16_set_option(crtfx_resize16* p, int option, int value) {
-    if (!p) return CRTFX_E_INVALID;
-    if (option != CRTFX_RESIZE16_OPT_FORCE_GENERAL) return fail(p, CRTFX_E_INVALID, "unknown resize16 option %d", option);
-    if (value != 0 && value != 1) return fail(p, CRTFX_E_INVALID, "FORCE_GENERAL takes 0 or 1, got %d", value);
-    p->force_general = value != 0;
-    note_plan(p, 0);
-    return CRTFX_OK;
-}
+int crtfx_resize16_set_option(crtfx_resize16* p, int option, int value) { return crtfx_resize::set_option<Unit>(p, option, value); }
 
-int crtfx_resize16_last_plan(crtfx_resize16* p, char* buf, size_t n) {
-    if (!p || !buf || n == 0) return CRTFX_E_INVALID;
-    snprintf(buf, n, "%s", p->plan);
-    return CRTFX_OK;
-}
+int crtfx_resize16_last_plan(crtfx_resize16* p, char* buf, size_t n) { return crtfx_resize::last_plan(p, buf, n); }
 
 int crtfx_resize16_run(crtfx_resize16* p, const void* src_base, size_t src_stride_bytes, void* dst_base, size_t dst_stride_bytes, int n, void* stream) {
-    if (!p) return CRTFX_E_INVALID;
-    if (!src_base || !dst_base) return fail(p, CRTFX_E_INVALID, "null frame pointer");
-    if (n < 1) return fail(p, CRTFX_E_INVALID, "n = %d frames", n);
-    if ((reinterpret_cast<uintptr_t>(src_base) | reinterpret_cast<uintptr_t>(dst_base) | src_stride_bytes | dst_stride_bytes) & 1u)
-        return fail(p, CRTFX_E_INVALID, "frame bases and strides must be even (16-bit elements)");
-    const size_t src_bytes = (size_t)p->sh * p->sw * 6, dst_bytes = (size_t)p->dh * p->dw * 6;
-    if (n > 1 && (src_stride_bytes < src_bytes || dst_stride_bytes < dst_bytes))
-        return fail(p, CRTFX_E_INVALID, "frame strides %zu / %zu bytes are smaller than a frame (%zu / %zu)", src_stride_bytes, dst_stride_bytes, src_bytes, dst_bytes);
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(p, CRTFX_E_HIP, "hipGetDevice failed");
-    if (dev != p->device) return fail(p, CRTFX_E_INVALID, "current device %d is not the plan's device %d (call hipSetDevice first)", dev, p->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint16_t* src = static_cast<const uint16_t*>(src_base);
-    uint16_t* dst = static_cast<uint16_t*>(dst_base);
-    const size_t ss = src_stride_bytes / 2, ds = dst_stride_bytes / 2;
-    const bool fused = p->fused_fits && !p->force_general;
-    const int group = fused ? 32768 : p->scratch_frames;          // grid.z; the general path's scratch
-    for (int f = 0; f < n; f += group) {
-        const int g = n - f < group ? n - f : group;
-        if (fused) {
-            Args a = p->fused;
-            a.x = p->x; a.y = p->y;
-            a.src = src + (size_t)f * ss; a.src_stride = ss;
-            a.dst = dst + (size_t)f * ds; a.dst_stride = ds;
-            dim3 grid((p->dw + a.TW - 1) / a.TW, (p->dh + a.TH - 1) / a.TH, g);
-            hipLaunchKernelGGL(k_resize16_fused, grid, dim3(BLOCK), (size_t)p->lds_bytes, st, a);
-        } else {
-            hipLaunchKernelGGL(k_resize16_h, dim3((p->dw + BLOCK - 1) / BLOCK, p->sh, g), dim3(BLOCK), 0, st,
-                               src + (size_t)f * ss, ss, p->scratch, p->sh, p->sw, p->dw, p->x);
-            hipLaunchKernelGGL(k_resize16_v, dim3((p->dw * 3 + BLOCK - 1) / BLOCK, p->dh, g), dim3(BLOCK), 0, st,
-                               p->scratch, dst + (size_t)f * ds, ds, p->sh, p->dw, p->y);
-        }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(p, CRTFX_E_HIP, "resize16 launch: %s", hipGetErrorString(e));
-    }
-    note_plan(p, n);
-    return CRTFX_OK;
+    return crtfx_resize::run<Unit>(p, src_base, src_stride_bytes, dst_base, dst_stride_bytes, n, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // crtfx_stage_host.h — the host skeleton of the format stages (crtfx_unpack.hip, crtfx_egress.hip, crtfx_deep.hip, crtfx_422.hip,
 // crtfx_444.hip, crtfx_sited.hip, crtfx_egress_sited.hip): what surrounds their kernels and does not depend on the format.  Host code only, and everything here is a template or
-// sits in an unnamed namespace, so every translation unit that includes it gets a copy of its own: the units still share no state.
+// sits in an unnamed namespace, so every translation unit that includes it gets a copy of its own: the units still share no state.  The resize
+// stages' skeleton (crtfx_resize_host.h) takes DeviceGuard, create_err and fail from here and nothing else.
 //
 // A unit brings its kernels, its Args, a plan `struct Plan : StagePlan { Args args{}; }`, its handle types (the plan itself or structures
 // derived from it) and a structure U of static members that the templates below take as a parameter, so that every call is a direct one:

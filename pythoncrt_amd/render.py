@@ -178,6 +178,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     import os
     import torch
     from .pipeline import FramePipeline, RenderSettings
+    from ._stage import resize_plan
     unknown = set(io_keywords) - set(_IO_KEYS)
     if unknown:
         raise TypeError(f"process_frames() got unexpected keyword arguments {sorted(unknown)}")
@@ -252,15 +253,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     out_shape = (B, dh, dw, 3) if egress is None else (B, egress.frame_bytes)  # what is downloaded and handed to the writer
     resize_out = None
     if deliver is not None:                                                    # the finished frames at the delivery size, between the chain and the egress plan
-        if deliver_filter != "bilinear":
-            from .resample import Resample
-            resize_out = Resample(dev, (h, w), (dh, dw), filter=deliver_filter, dtype=pix)
-        elif deep:
-            from .resize16 import ResizeHalf
-            resize_out = ResizeHalf(dev, (h, w), (dh, dw))
-        else:
-            from .ingest import IngestResize
-            resize_out = IngestResize(dev, (h, w), (dh, dw))
+        resize_out = resize_plan(dev, (h, w), (dh, dw), deliver_filter, pix)
     pin_out = [torch.empty(out_shape, dtype=torch.uint8).pin_memory() for _ in range(NS)]
     dev_in = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]
     dev_out = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]
@@ -278,11 +271,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
 
     def resize_in(src_hw):
         """The plan that brings uint8 RGB frames of a source size to the render size: IngestResize, or Resample under another in_filter."""
-        if in_filter != "bilinear":
-            from .resample import Resample
-            return Resample(dev, src_hw, (h, w), filter=in_filter, dtype=torch.uint8)
-        from .ingest import IngestResize
-        return IngestResize(dev, src_hw, (h, w))
+        return resize_plan(dev, src_hw, (h, w), in_filter, torch.uint8)
 
     MAX_SOURCES = 4                  # source sizes whose staging buffers and ingest plan are kept
     sources = {}                     # (src_h, src_w) -> _Source, in order of last use

@@ -83,3 +83,56 @@ def test_generated_symbol_tables_equal_the_literal_seven(table, families):
     for fam in families:                                                       # the classes call exactly these families
         users = [c for f in formats.FORMATS.values() for c in (f.source, f.egress) if c._family == fam]
         assert users, fam
+
+
+def _literal_resize(fam):
+    vp = ctypes.c_void_p
+    return {
+        f"crtfx_{fam}_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int,
+                                               vp, vp, vp, ctypes.c_int, ctypes.POINTER(vp)]),
+        f"crtfx_{fam}_destroy": (ctypes.c_int, [vp]),
+        f"crtfx_{fam}_last_error": (ctypes.c_char_p, [vp]),
+        f"crtfx_{fam}_run": (ctypes.c_int, [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_int, vp]),
+        f"crtfx_{fam}_set_option": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
+        f"crtfx_{fam}_last_plan": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t]),
+    }
+
+
+@pytest.mark.parametrize("table,family,cls,option", [("INGEST_SYMBOLS", "ingest", "IngestResize", "INGEST_OPT_FORCE_GENERAL"),
+                                                     ("RESIZE16_SYMBOLS", "resize16", "ResizeHalf", "RESIZE16_OPT_FORCE_GENERAL"),
+                                                     ("RESAMPLE_SYMBOLS", "resample", "Resample", "RESAMPLE_OPT_FORCE_GENERAL")])
+def test_generated_resize_symbol_tables_equal_the_literal_six(table, family, cls, option):
+    """_lib.resize_symbols against the six entry points of a resize stage written out, contents and order; _lib.load() binds them; the
+    plan class calls exactly this family, and its force option is the family's *_OPT_FORCE_GENERAL."""
+    import pythoncrt_amd as pc
+    from pythoncrt_amd import _stage
+    want = _literal_resize(family)
+    got = getattr(_lib, table)
+    assert got == want and len(got) == 6 and list(got) == list(want)
+    assert got == _lib.resize_symbols(family)
+    assert list(_lib.resize_symbols("ingest", "resample")) == list(_literal_resize("ingest")) + list(_literal_resize("resample"))
+    lib = _lib.load()
+    for name, (res, args) in want.items():
+        assert getattr(lib, name).restype == res and getattr(lib, name).argtypes == args, name
+    plan = getattr(pc, cls)
+    assert issubclass(plan, _stage.ResizePlan) and issubclass(plan, _stage.Handle) and not issubclass(plan, _stage.StagePlan)
+    assert plan._family == family and plan._force_option == 1 == getattr(_lib, option)
+
+
+@pytest.mark.parametrize("family,pix,filter", [("ingest", _lib.PIX_U8, "bilinear"), ("resize16", _lib.PIX_F16, "bilinear"),
+                                               ("resample", _lib.PIX_U8, "bicubic"), ("resample", _lib.PIX_F16, "bicubic")])
+def test_the_tall_case_of_the_resize_api_test_passes_the_table_checks(family, pix, filter):
+    """2048 x 4 -> 1 x 4, the pair tests/test_resize_api_gpu.py takes for the general path by necessity: its tables pass every check of
+    crtfx_<family>_create (the call gets as far as the device, and device 4096 exists on no machine), and each row of the 2048 the one
+    output row reaches costs at least 32 bytes of LDS, more than the budget of 40 960 bytes for any tile shape."""
+    from pythoncrt_amd import tables
+    src, dst = (2048, 4), (1, 4)
+    axis = tables.pil_resample_axis if filter == "bilinear" else (lambda a, b: tables.pil_filter_axis(a, b, filter))
+    ax, ay = axis(src[1], dst[1]), axis(src[0], dst[0])
+    assert int(ay[0][0]) == 0 and int(ay[1][0]) == 2048 and 2048 * 32 > 40960
+    lib = _lib.load()
+    plan = ctypes.c_void_p(1)
+    rc = getattr(lib, f"crtfx_{family}_create")(4096, src[0], src[1], dst[0], dst[1], pix, tables.ptr(ax[0]), tables.ptr(ax[1]), tables.ptr(ax[2]), ax[2].shape[1],
+                                                tables.ptr(ay[0]), tables.ptr(ay[1]), tables.ptr(ay[2]), ay[2].shape[1], ctypes.byref(plan))
+    msg = (getattr(lib, f"crtfx_{family}_last_error")(None) or b"").decode()
+    assert rc == _lib.E_HIP and not plan.value and msg == "no HIP device 4096", (rc, msg)
