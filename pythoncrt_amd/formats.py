@@ -5,7 +5,7 @@ from __future__ import annotations
 
 from typing import Callable, NamedTuple, Tuple
 
-from . import deep, deep444, egress, unpack, yuv422
+from . import deep, deep444, egress, sited, unpack, yuv422
 
 
 class Family(NamedTuple):
@@ -33,3 +33,19 @@ def bits(fmt: str) -> int:
 def frame_bytes(h: int, w: int, fmt: str) -> int:
     """Bytes of one packed h x w frame of `fmt` (a member of PIX_FMTS), rows unpadded."""
     return FORMATS[fmt].frame_bytes(int(h), int(w), fmt) if fmt in FORMATS else int(h) * int(w) * 3
+
+
+def source_plan(device, size, fmt: str, matrix: str, range: str, chroma: str):     # noqa: A002 - the stages' keyword
+    """The plan in front of the chain: None for "rgb24", the family's source under chroma "replicate", else UnpackSited at that siting."""
+    if fmt == "rgb24":
+        return None
+    cls, siting = (FORMATS[fmt].source, {}) if chroma == "replicate" else (sited.UnpackSited, {"siting": chroma})
+    return cls(device, size, layout=fmt, matrix=matrix, range=range, **siting)
+
+
+def egress_plan(device, size, fmt: str, matrix: str, range: str, chroma: str):     # noqa: A002
+    """The plan behind the chain: None for "rgb24", the family's egress under chroma "center" (the box mean), else EgressSited at "left"."""
+    if fmt == "rgb24":
+        return None
+    cls, siting = (FORMATS[fmt].egress, {}) if chroma == "center" else (sited.EgressSited, {"siting": chroma})
+    return cls(device, size, layout=fmt, matrix=matrix, range=range, **siting)

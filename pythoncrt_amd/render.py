@@ -16,6 +16,7 @@ frames of a batch go to the GPU together (pinned staging, upload / kernels / dow
 writes of batch k - 1 and reads of batch k + 1) instead of one `apply_static_effects` call per frame on two worker threads."""
 from __future__ import annotations
 
+import contextlib
 from typing import Callable, Iterable, Optional, Tuple
 
 import numpy as np
@@ -178,7 +179,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     import os
     import torch
     from .pipeline import FramePipeline, RenderSettings
-    from ._stage import resize_plan
+    from .ends import DeliveryEnd, SourceEnd, StagingSlots
     unknown = set(io_keywords) - set(_IO_KEYS)
     if unknown:
         raise TypeError(f"process_frames() got unexpected keyword arguments {sorted(unknown)}")
@@ -220,7 +221,6 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         raise RuntimeError("no ROCm device visible; pythoncrt_amd has no CPU fallback")
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     h, w, B = int(out_h), int(out_w), max(1, int(batch))
-    dh, dw = deliver if deliver is not None else (h, w)
     rs = RenderSettings(
         scanline_strength=float(scanline_strength), triad_strength=float(triad_strength), triad_gamma=float(triad_gamma),
         triad_preserve_luma=bool(triad_preserve_luma), triad_softness=float(triad_softness), aberration_px=int(aberration_px),
@@ -241,85 +241,26 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     total = max(1, int(total_frames)) if total_frames else None
 
     NS = 2
-    # a 4:2:0 / 4:2:2 input is staged in slots of its own size (_YuvSource below): no rgb24-sized pinned slot is needed then
-    pin_in = [torch.empty((B, h, w, 3), dtype=torch.uint8).pin_memory() if in_pix_fmt == "rgb24" else torch.empty((0, h, w, 3), dtype=torch.uint8)
-              for _ in range(NS)]
-    egress = None
-    if out_pix_fmt != "rgb24":                                                 # the encoder's format: converted on the device, half the bytes downloaded
-        if out_chroma == "center":
-            egress = formats.FORMATS[out_pix_fmt].egress(dev, (dh, dw), layout=out_pix_fmt, matrix=out_matrix, range=out_range)
-        else:
-            egress = sited.EgressSited(dev, (dh, dw), layout=out_pix_fmt, matrix=out_matrix, range=out_range, siting=out_chroma)
-    out_shape = (B, dh, dw, 3) if egress is None else (B, egress.frame_bytes)  # what is downloaded and handed to the writer
-    resize_out = None
-    if deliver is not None:                                                    # the finished frames at the delivery size, between the chain and the egress plan
-        resize_out = resize_plan(dev, (h, w), (dh, dw), deliver_filter, pix)
-    pin_out = [torch.empty(out_shape, dtype=torch.uint8).pin_memory() for _ in range(NS)]
+    pin_in = [torch.empty((B, h, w, 3), dtype=torch.uint8).pin_memory() for _ in range(NS)] if in_pix_fmt == "rgb24" else None   # else: a SourceEnd's own
+    end =DeliveryEnd(dev, (h, w), pix, out_pix_fmt, out_matrix, out_range, out_chroma, deliver, deliver_filter)
+    pin_out = [torch.empty(end.shape(B), dtype=torch.uint8).pin_memory() for _ in range(NS)]    # what is downloaded and handed to the writer
     dev_in = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]
     dev_out = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]
-    dev_fin = dev_out if resize_out is None else [torch.empty((B, dh, dw, 3), dtype=pix, device=dev) for _ in range(NS)]   # what the egress plan / the download reads
-    dev_yuv = [torch.empty(out_shape, dtype=torch.uint8, device=dev) for _ in range(NS)] if egress is not None else None
-    np_in = [t.numpy() for t in pin_in]
+    end.slots(dev_out)
     np_out = [t.numpy() for t in pin_out]
-    compute = torch.cuda.current_stream(dev)
-    s_up, s_down = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
-    up_done = [None] * NS            # the upload that last read pin_in[d]
-    kernels_done = [None] * NS       # the kernels that last read dev_in[d] / wrote dev_out[d]
+    compute, s_up, s_down = torch.cuda.current_stream(dev), torch.cuda.Stream(dev), torch.cuda.Stream(dev)
+    # rgb24 frames at render size are uploaded straight into dev_in.  Their kernels_done is the GLOBAL list: EVERY batch records its event there,
+    # because every batch — an off-size one through its convert and the chain — reads dev_in[d]; an off-size source's own list covers ITS dev[d].
+    direct = StagingSlots().adopt(dev_in, pin_in)
     down_done = [None] * NS          # the download that last read dev_out[d]
-    state, index, written, k = None, 0, 0, 0
-    pending = None                   # (slot, frames, download event) of the batch whose frames are still to be written
-
-    def resize_in(src_hw):
-        """The plan that brings uint8 RGB frames of a source size to the render size: IngestResize, or Resample under another in_filter."""
-        return resize_plan(dev, src_hw, (h, w), in_filter, torch.uint8)
+    state, index, written, k, pending = None, 0, 0, 0, None      # pending: (slot, frames, download event) of the batch still to be written
 
     MAX_SOURCES = 4                  # source sizes whose staging buffers and ingest plan are kept
-    sources = {}                     # (src_h, src_w) -> _Source, in order of last use
+    sources = {}                     # (src_h, src_w) -> SourceEnd, in order of last use
     carry = None                     # a frame already taken from the iterator that starts the next batch (its source size differs)
-
-    class _Source:
-        """Staging of one off-size source: pinned and device slots of ITS size, the plan that resizes them into dev_in[d]."""
-        def __init__(self, sh, sw):
-            self.plan = resize_in((sh, sw))
-            self.pin = [torch.empty((B, sh, sw, 3), dtype=torch.uint8).pin_memory() for _ in range(NS)]
-            self.dev = [torch.empty((B, sh, sw, 3), dtype=torch.uint8, device=dev) for _ in range(NS)]
-            self.np = [t.numpy() for t in self.pin]
-            self.up_done = [None] * NS           # the upload that last read pin[d]
-            self.kernels_done = [None] * NS      # the resize that last read dev[d]
-
-        def convert(self, d, n):
-            self.plan.run(self.dev[d][:n], out=dev_in[d][:n])                          # ref:1039-1041
-
-    YUV = "yuv"                      # the key of the one 4:2:0 / 4:2:2 source (its size is fixed by in_size)
+    YUV = "yuv"                      # the key of the one 4:2:0 / 4:2:2 source (its size is fixed by in_size): a SourceEnd
     yuv_hw = (h, w) if in_size is None else (int(in_size[0]), int(in_size[1]))
     yuv_bytes = formats.frame_bytes(yuv_hw[0], yuv_hw[1], in_pix_fmt)
-
-    class _YuvSource:
-        """Staging of a 4:2:0 or 4:2:2 input: pinned and device slots of frame_bytes(*in_size) bytes per frame, the plan that converts them to RGB —
-        into dev_in[d] itself, or, where in_size is not the output size, into RGB slots of that size which IngestResize brings to dev_in[d]."""
-        def __init__(self):
-            if in_chroma == "replicate":
-                self.plan = formats.FORMATS[in_pix_fmt].source(dev, yuv_hw, layout=in_pix_fmt, matrix=in_matrix, range=in_range)
-            else:
-                self.plan = sited.UnpackSited(dev, yuv_hw, layout=in_pix_fmt, matrix=in_matrix, range=in_range, siting=in_chroma)
-            self.nbytes = self.plan.frame_bytes
-            assert self.nbytes == yuv_bytes
-            self.resize, self.rgb = None, None
-            if yuv_hw != (h, w):
-                self.resize = resize_in(yuv_hw)
-                self.rgb = [torch.empty((B,) + yuv_hw + (3,), dtype=torch.uint8, device=dev) for _ in range(NS)]
-            self.pin = [torch.empty((B, self.nbytes), dtype=torch.uint8).pin_memory() for _ in range(NS)]
-            self.dev = [torch.empty((B, self.nbytes), dtype=torch.uint8, device=dev) for _ in range(NS)]
-            self.np = [t.numpy() for t in self.pin]
-            self.up_done = [None] * NS           # the upload that last read pin[d]
-            self.kernels_done = [None] * NS      # the conversion that last read dev[d] (and, on the same stream, the resize that read rgb[d])
-
-        def convert(self, d, n):
-            if self.resize is None:
-                self.plan.run(self.dev[d][:n], out=dev_in[d][:n])
-            else:
-                self.plan.run(self.dev[d][:n], out=self.rgb[d][:n])
-                self.resize.run(self.rgb[d][:n], out=dev_in[d][:n])
 
     def source(key):
         src = sources.pop(key, None)
@@ -327,7 +268,9 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
             if len(sources) >= MAX_SOURCES:      # rare: drop the least recently used size once its queued work is done
                 torch.cuda.synchronize(dev)
                 sources.pop(next(iter(sources)))
-            src = _YuvSource() if key == YUV else _Source(*key)
+            fmt, hw = (in_pix_fmt, yuv_hw) if key == YUV else ("rgb24", key)
+            src = SourceEnd(dev, (h, w), fmt, in_matrix, in_range, in_chroma, hw, in_filter).slots(B, NS)
+            assert key != YUV or src.frame_bytes == yuv_bytes
         sources[key] = src
         return src
 
@@ -365,9 +308,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         done = False
         while not done:
             d = k % NS
-            if up_done[d] is not None:
-                up_done[d].synchronize()             # the upload that read this pinned slot two batches ago (long done)
-            n, key, src, slot = 0, None, None, np_in[d]
+            n, key, src = 0, None, None
             while n < B:
                 if carry is not None:
                     (a, akey), carry = carry, None
@@ -379,54 +320,37 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                         break
                     a, akey = fit(frame)
                 if n == 0:
-                    key = akey
-                    if key is not None:                  # an off-size batch is staged at ITS size
-                        src = source(key)
-                        if src.up_done[d] is not None:
-                            src.up_done[d].synchronize()
-                        slot = src.np[d]
+                    key, src = akey, direct if akey is None else source(akey)      # an off-size batch is staged at ITS size
+                    if src.up_done[d] is not None:
+                        src.up_done[d].synchronize()     # the upload that read this pinned slot two batches ago (long done)
+                    slot = src.np[d]
                 elif akey != key:                        # the source size changes: this frame opens the next batch
                     carry = (a, akey)
                     break
                 np.copyto(slot[n], a, casting="unsafe")
                 n += 1
             if n:
-                if src is None:
-                    if kernels_done[d] is not None:
-                        s_up.wait_event(kernels_done[d])
-                    with torch.cuda.stream(s_up):
-                        dev_in[d][:n].copy_(pin_in[d][:n], non_blocking=True)
-                        up = torch.cuda.Event()
-                        up.record(s_up)
-                    up_done[d] = up
-                    compute.wait_event(up)
-                else:
-                    if src.kernels_done[d] is not None:
-                        s_up.wait_event(src.kernels_done[d])
-                    with torch.cuda.stream(s_up):
-                        src.dev[d][:n].copy_(src.pin[d][:n], non_blocking=True)
-                        up = torch.cuda.Event()
-                        up.record(s_up)
-                    src.up_done[d] = up
-                    compute.wait_event(up)
-                    # dev_in[d]: its last upload (two batches ago) was awaited by `compute` then, its last readers ran on `compute`
-                    src.convert(d, n)                                                # on the compute stream
+                if src.kernels_done[d] is not None:      # the kernels that last read src.dev[d]: for `direct`, those of whichever batch came last
+                    s_up.wait_event(src.kernels_done[d])
+                with torch.cuda.stream(s_up):
+                    src.dev[d][:n].copy_(src.pin[d][:n], non_blocking=True)
+                    up = torch.cuda.Event()
+                    up.record(s_up)
+                src.up_done[d] = up
+                compute.wait_event(up)
+                # dev_in[d]: its last upload (two batches ago) was awaited by `compute` then, its last readers ran on `compute`
+                src.convert(d, n, dev_in[d][:n])                                     # on the compute stream; nothing for `direct`
                 if down_done[d] is not None:
                     compute.wait_event(down_done[d])
                 _, state = pipe.run(dev_in[d][:n], first_index=index, state=state, out=dev_out[d][:n])
-                if resize_out is not None:           # behind the chain on the compute stream; dev_fin[d]'s last reader (egress on this stream, or
-                    resize_out.run(dev_out[d][:n], out=dev_fin[d][:n])    # the download awaited above) is done
-                if egress is not None:               # behind the chain on the compute stream; dev_yuv[d]'s last download was awaited above
-                    egress.run(dev_fin[d][:n], out=dev_yuv[d][:n])
+                send = end.run(d, n)                 # behind the chain on the compute stream; the slot's last download was awaited above
                 kd = torch.cuda.Event()
                 kd.record(compute)
-                kernels_done[d] = kd
-                if src is not None:
-                    src.kernels_done[d] = kd
+                direct.kernels_done[d] = src.kernels_done[d] = kd      # the kernels that last read dev_in[d] / wrote dev_out[d]
                 # pin_out[d] was drained one iteration ago (drain below runs before the next batch is enqueued into the same slot)
                 s_down.wait_event(kd)
                 with torch.cuda.stream(s_down):
-                    pin_out[d][:n].copy_((dev_fin if egress is None else dev_yuv)[d][:n], non_blocking=True)
+                    pin_out[d][:n].copy_(send, non_blocking=True)
                     dn = torch.cuda.Event()
                     dn.record(s_down)
                 down_done[d] = dn
@@ -441,10 +365,8 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         if pending is not None:
             drain(pending)
     except BaseException:
-        try:
+        with contextlib.suppress(Exception):     # the caller's exception is the one to report
             torch.cuda.synchronize(dev)          # uploads / kernels / downloads still in flight reference the buffers above
-        except Exception:       # noqa: BLE001 - the caller's exception is the one to report
-            pass
         raise
     if progress_cb is not None and not total:
         progress_cb(1.0)
