@@ -12,11 +12,13 @@
     from pythoncrt_amd import EgressSited         # ... and the egress step of the same formats with chroma filtered onto that siting instead of box-averaged
     from pythoncrt_amd import ResizeHalf          # IngestResize for half frames: behind the chain, where process_frames(deliver_size=) delivers another size
     from pythoncrt_amd import Resample            # either of the two with a filter: box / bilinear / hamming / bicubic / lanczos, uint8 or half frames
+    from pythoncrt_amd import Canvas              # crop and pad: a window of uint8 or half frames placed on a canvas of another size, the rest a colour
 
 See DESIGN.md (path, kernels, roofline) and INTEGRATION.md (how the reference binds to it).
 """
 from .effects import (DeviceState, TriadMask, VignetteMask, apply_crt_effect, apply_static_effects, make_triad_mask,
                       make_vignette)
+from .canvas import Canvas
 from .deep import EgressYuv10, UnpackYuv10
 from .deep444 import EgressDeep444, UnpackDeep444
 from .egress import EgressYuv
@@ -30,4 +32,4 @@ from .yuv422 import EgressYuv422, UnpackYuv422
 
 __all__ = ["DeviceState", "TriadMask", "VignetteMask", "apply_crt_effect", "apply_static_effects", "make_triad_mask", "make_vignette",
            "process_frames", "iter_rgb24", "iter_yuv420", "IngestResize", "EgressYuv", "UnpackYuv", "EgressYuv10", "UnpackYuv10",
-           "iter_yuv422", "EgressYuv422", "UnpackYuv422", "iter_deep444", "EgressDeep444", "UnpackDeep444", "UnpackSited", "EgressSited", "ResizeHalf", "Resample"]
+           "iter_yuv422", "EgressYuv422", "UnpackYuv422", "iter_deep444", "EgressDeep444", "UnpackDeep444", "UnpackSited", "EgressSited", "ResizeHalf", "Resample", "Canvas"]

@@ -59,6 +59,11 @@ With a 4:2:0 / 4:2:2 `--out-pix-fmt`, `--out-chroma left` filters every chroma s
 chroma_location=left (or nothing) and the only siting 4:2:2 defines; pass `-chroma_sample_location left` to the encoder.  The default
 `center` writes the 2 x 2 / 2 x 1 box mean as before (ffprobe's chroma_location=center: JPEG / MPEG-1).
 
+`--in-crop-x / -y / -width / -height` cut a window out of every input frame on the GPU (include/crtfx_canvas.h) and resize it back to
+`--width x --height` (a letterboxed source: the picture area fills the tube); with `--deliver-width` / `--deliver-height`, `--deliver-fit pad`
+centres the render, resized to fit, on a frame of `--deliver-pad-color` (a 4:3 render pillarboxed in 16:9) and `--deliver-fit crop` cuts the
+centred window of the delivery's aspect; the default `stretch` is the path as it was.
+
 `--gui`, `--gpu`, `--nvenc-preset`, `--encoder`, `--decoder`, `--crf` and `--bitrate` are accepted for
 compatibility and ignored (encode/decode/UI are not part of this path).  `--text*` rasterise the overlay on
 the host with Pillow (ref:366-414) and alpha-blend it on the GPU before or after the effects.
@@ -177,6 +182,11 @@ def add_output_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--deliver-filter", type=str, default="bilinear", choices=list(tables.RESAMPLE_FILTERS),
                    help="filter of the --deliver-width / --deliver-height resize: Pillow's BILINEAR (default) or another of its five, e.g. lanczos or "
                         "bicubic for a 4K render written as 1080p; needs a delivery size other than the render size")
+    p.add_argument("--deliver-fit", type=str, default="stretch", choices=["stretch", "pad", "crop"],
+                   help="how the render meets a --deliver-width x --deliver-height of another aspect: stretch it (default), pad: resize it to fit "
+                        "inside and centre it on a frame of --deliver-pad-color (a 4:3 render pillarboxed in 16:9), or crop: cut the centred window "
+                        "of the delivery's aspect and resize that; on the GPU (include/crtfx_canvas.h); needs a delivery size other than the render size")
+    p.add_argument("--deliver-pad-color", type=str, default="0,0,0", help="R,G,B of the bars of --deliver-fit pad, each 0..255 (default 0,0,0)")
     return p
 
 
@@ -190,6 +200,40 @@ def deliver_size_from_args(a):
     if min(dh, dw) < 1 or max(dh, dw) > 32767:
         raise SystemExit(f"--deliver-width {dw} --deliver-height {dh}: sizes outside 1..32767")
     return None if (dh, dw) == (int(a.height), int(a.width)) else (dh, dw)
+
+
+def pad_color_from_args(a):
+    """(r, g, b) of --deliver-pad-color."""
+    text = str(getattr(a, "deliver_pad_color", "0,0,0"))
+    try:
+        vals = tuple(int(v) for v in text.split(","))
+    except ValueError:
+        vals = ()
+    if len(vals) != 3 or min(vals) < 0 or max(vals) > 255:
+        raise SystemExit(f"--deliver-pad-color {text}: three integers R,G,B in 0..255")
+    return vals
+
+
+def in_crop_from_args(a):
+    """(y, x, h, w) of --in-crop-y / -x / -height / -width, or None.  A window needs both sides; 0 (default) everywhere = none."""
+    x, y, cw, ch = (int(getattr(a, "in_crop_" + k, 0) or 0) for k in ("x", "y", "width", "height"))
+    if (cw == 0) != (ch == 0) or (cw == 0 and (x or y)):
+        raise SystemExit("--in-crop-x, --in-crop-y, --in-crop-width and --in-crop-height go together: pass a window with both sides, or none of them "
+                         "(0 = no crop)")
+    if cw == 0:
+        return None
+    if min(cw, ch) < 1 or min(x, y) < 0 or x + cw > int(a.width) or y + ch > int(a.height):
+        raise SystemExit(f"--in-crop-x {x} --in-crop-y {y} --in-crop-width {cw} --in-crop-height {ch}: the window leaves the "
+                         f"--width {a.width} x --height {a.height} input")
+    return y, x, ch, cw
+
+
+def check_fit_flags(a, deliver) -> None:
+    """--deliver-fit other than stretch needs a delivery size of its own to fit to (`deliver` is deliver_size_from_args(a))."""
+    pad_color_from_args(a)
+    if getattr(a, "deliver_fit", "stretch") != "stretch" and deliver is None:
+        raise SystemExit(f"--deliver-fit {a.deliver_fit} without --deliver-width / --deliver-height other than the render size: "
+                         "there is nothing to fit")
 
 
 def check_filter_flags(a, deliver) -> None:
@@ -216,6 +260,13 @@ def add_input_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
                    help="filter of the resize that brings a source of another size to --width x --height (process_frames(in_filter=)): Pillow's "
                         "BILINEAR (default) or another of its five; a raw input file is read at --width x --height, so nothing is resized in "
                         "front of the chain here")
+    p.add_argument("--in-crop-x", type=int, default=0,
+                   help="left column of a window of the --width x --height input that is cut out on the GPU (include/crtfx_canvas.h) and resized back "
+                        "to --width x --height for the render (a letterboxed source: the picture area fills the tube); with --in-crop-y, "
+                        "--in-crop-width and --in-crop-height; all 0 (default) = no crop")
+    p.add_argument("--in-crop-y", type=int, default=0, help="top row of the window (see --in-crop-x)")
+    p.add_argument("--in-crop-width", type=int, default=0, help="width of the window (see --in-crop-x); 0 (default) = no crop")
+    p.add_argument("--in-crop-height", type=int, default=0, help="height of the window (see --in-crop-x); 0 (default) = no crop")
     return p
 
 
@@ -264,6 +315,12 @@ def main_sharded(a, rank: int, world: int) -> int:
         # every rank writes its chunks at offsets of its own: those, and the downloads behind them, are at render size here
         raise SystemExit("--deliver-width / --deliver-height are not supported by the sharded CLI (one process per GPU writes rgb24 at render size); "
                          "run one process, or scale behind it")
+    for flag, on in (("--in-crop-x / --in-crop-y / --in-crop-width / --in-crop-height", any(getattr(a, "in_crop_" + k, 0) for k in ("x", "y", "width", "height"))),
+                     ("--deliver-fit", getattr(a, "deliver_fit", "stretch") != "stretch"),
+                     ("--deliver-pad-color", str(getattr(a, "deliver_pad_color", "0,0,0")) != "0,0,0")):
+        if on:
+            raise SystemExit(f"{flag} is not supported by the sharded CLI (one process per GPU reads and writes rgb24 at render size); "
+                             "run one process, or crop / pad outside it")
     for flag, value in (("--in-filter", getattr(a, "in_filter", "bilinear")), ("--deliver-filter", getattr(a, "deliver_filter", "bilinear"))):
         if value != "bilinear":
             raise SystemExit(f"{flag} {value} is not supported by the sharded CLI (one process per GPU reads and writes rgb24 at render size: "
@@ -416,6 +473,7 @@ def check_flags(a):
             raise SystemExit("pass --input, --width and --height")
         return deliver, None, (int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")))
     check_filter_flags(a, deliver)
+    check_fit_flags(a, deliver)
     if a.gui or not a.input:
         raise SystemExit("the GUI is not part of this path; pass --input (raw rgb24 / yuv420p / nv12 / yuv422p / yuyv422 / uyvy422 / yuv420p10le / p010le / yuv444p10le / gbrp10le / x2rgb10le file or '-')")
     if a.width <= 0 or a.height <= 0:
@@ -425,6 +483,10 @@ def check_flags(a):
         raise SystemExit(f"--in-pix-fmt {a.in_pix_fmt} with --out-pix-fmt {a.out_pix_fmt}: a 10-bit format on one end only; the chain between them "
                          "runs on half pixels or on uint8 ones — pass yuv420p10le / p010le (or yuv444p10le / gbrp10le / x2rgb10le) on both ends "
                          "or on neither")
+    crop = in_crop_from_args(a)
+    if deep and crop is not None and crop[2:] != (int(a.height), int(a.width)):
+        raise SystemExit(f"--in-crop-width {crop[3]} --in-crop-height {crop[2]} differs from --width {a.width} x --height {a.height}: a 10-bit input "
+                         "cannot be resized (IngestResize has no half path)")
     return deliver, deep, None
 
 
@@ -606,13 +668,15 @@ def main(argv=None) -> int:
     fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb", buffering=0)
     out_path = a.output if a.output else (a.input + "_crt.rgb" if a.input != "-" else "-")
     B, NS = max(1, int(a.batch)), 3
-    end = DeliveryEnd(dev, (h, w), pix, a.out_pix_fmt, a.out_matrix, a.out_range, a.out_chroma, deliver, a.deliver_filter)
-    source = SourceEnd(dev, (h, w), a.in_pix_fmt, a.in_matrix, a.in_range, a.in_chroma, (h, w), a.in_filter) if a.in_pix_fmt != "rgb24" else None
+    end = DeliveryEnd(dev, (h, w), pix, a.out_pix_fmt, a.out_matrix, a.out_range, a.out_chroma, deliver, a.deliver_filter, a.deliver_fit, pad_color_from_args(a))
+    crop = in_crop_from_args(a)                                    # a window of the input: an rgb24 input then has a source end too
+    source = (SourceEnd(dev, (h, w), a.in_pix_fmt, a.in_matrix, a.in_range, a.in_chroma, (h, w), a.in_filter, crop, pix)
+              if a.in_pix_fmt != "rgb24" or crop is not None else None)
     in_bytes = h * w * 3 if source is None else source.frame_bytes
     t0 = time.perf_counter()
     fout, in_pos, out_pos, pipes, out_plan = open_output(a, fin, out_path, B, in_bytes, end.frame_bytes)
     jobs = ((k * B * in_bytes if in_pos else None, B) for k in itertools.count())     # whole batches until the stream ends (the reader stops at a short read)
-    reader = _Reader(fin, in_pos, jobs, (B, h, w, 3) if source is None else (B, in_bytes), in_bytes, slots=NS, io=a.io, autostart=False)
+    reader = _Reader(fin, in_pos, jobs, (B, h, w, 3) if source is None else (B,) + source.frame_shape, in_bytes, slots=NS, io=a.io, autostart=False)
     writer = _Writer(fout, out_pos, end.shape(B), end.frame_bytes, slots=NS, plan=out_plan, io=a.io)
     t_pipe = time.perf_counter()                                    # the pipeline proper: first read issued ... last batch written (the --staging-report line)
     t_slots = t_pipe - t_start - t_imports - t_engine

@@ -2,6 +2,7 @@
 
 from . import formats
 from ._stage import resize_plan
+from .canvas import Canvas, fit_crop, fit_pad
 
 
 class StagingSlots:
@@ -20,40 +21,70 @@ class StagingSlots:
 
 
 class SourceEnd(StagingSlots):
-    """Frames of `in_pix_fmt` at `src_hw`, staged at THEIR size: [source plan] (none for rgb24), RGB slots of src_hw, [resize] (ref:1039-1041)."""
+    """Frames of `in_pix_fmt` at `src_hw`, staged at THEIR size: [source plan] (none for rgb24), RGB slots of src_hw, [Canvas cutting the
+    window `crop` = (y, x, ch, cw) of the source frame], [resize of what is left to the render size] (ref:1039-1041).  The RGB side of the
+    source plan, the window and the resize are frames of `dtype`."""
 
-    def __init__(self, device, render_hw, in_pix_fmt, in_matrix, in_range, in_chroma, src_hw, in_filter):
+    def __init__(self, device, render_hw, in_pix_fmt, in_matrix, in_range, in_chroma, src_hw, in_filter, crop=None, dtype=None):
         import torch
         self.device, self.src_hw = device, tuple(src_hw)
+        self.dtype = torch.uint8 if dtype is None else dtype
         self.plan = formats.source_plan(device, self.src_hw, in_pix_fmt, in_matrix, in_range, in_chroma)
-        self.resize = resize_plan(device, self.src_hw, render_hw, in_filter, torch.uint8) if self.src_hw != tuple(render_hw) else None
+        self.canvas, cut = None, self.src_hw
+        if crop is not None:
+            cut = (int(crop[2]), int(crop[3]))
+            self.canvas = Canvas(device, self.src_hw, cut, window=tuple(int(v) for v in crop), dtype=self.dtype)
+        self.resize = resize_plan(device, cut, render_hw, in_filter, self.dtype) if cut != tuple(render_hw) else None
         self.frame_bytes = formats.frame_bytes(*self.src_hw, in_pix_fmt) if self.plan is None else self.plan.frame_bytes
         self.frame_shape = self.src_hw + (3,) if self.plan is None else (self.frame_bytes,)
+        # the stages present, each with the size of the RGB frames it writes; the last one writes the chain's input
+        self.stages = [(st, hw) for st, hw in ((self.plan, self.src_hw), (self.canvas, cut), (self.resize, tuple(render_hw))) if st is not None]
 
     def slots(self, B: int, NS: int, pinned: bool = True):
         import torch
         shape = (B,) + self.frame_shape
-        if self.plan is not None and self.resize is not None:
-            self.rgb = [torch.empty((B,) + self.src_hw + (3,), dtype=torch.uint8, device=self.device) for _ in range(NS)]
+        # a stage that is not the last one writes RGB slots of its own: a missing stage costs no buffer
+        self.mid = [[torch.empty((B,) + hw + (3,), dtype=self.dtype, device=self.device) for _ in range(NS)] for _, hw in self.stages[:-1]]
         return self.adopt([torch.empty(shape, dtype=torch.uint8, device=self.device) for _ in range(NS)],
                           [torch.empty(shape, dtype=torch.uint8).pin_memory() for _ in range(NS)] if pinned else None)
 
     def convert(self, d: int, n: int, dst):
-        rgb = self.dev[d][:n]
-        if self.plan is not None:
-            rgb = self.plan.run(rgb, out=dst if self.resize is None else self.rgb[d][:n])
-        if self.resize is not None:
-            self.resize.run(rgb, out=dst)
+        x = self.dev[d][:n]
+        for i, (stage, _) in enumerate(self.stages):
+            x = stage.run(x, out=dst if i == len(self.stages) - 1 else self.mid[i][d][:n])
 
 
 class DeliveryEnd:
-    """Behind the chain: [the delivery resize] then [the egress plan, built for the delivery size].  `deliver` is None (as rendered) or a
-    validated (dh, dw); `pix` is the chain's dtype.  Everything downstream is in frames of `frame_bytes`, batches of `shape(B)`."""
+    """Behind the chain: [the delivery geometry: a resize, a Canvas, or both] then [the egress plan, built for the delivery size].
+    `deliver` is None (as rendered) or a validated (dh, dw); `pix` is the chain's dtype.  `deliver_fit` says how a render of another aspect
+    meets the delivery: "stretch" resizes it to (dh, dw); "pad" resizes it to fit_pad's inner size (no resize where that is the render
+    size) and a Canvas centres that on a (dh, dw) frame of `pad_color`; "crop" has a Canvas cut fit_crop's window and resizes that to
+    (dh, dw) (no resize where the window has that size).  Where the aspects agree — inner = delivery, window = the whole render — no
+    Canvas is built and the stages are those of "stretch".  Everything downstream is in frames of `frame_bytes`, batches of `shape(B)`."""
 
-    def __init__(self, device, render_hw, pix, out_pix_fmt, out_matrix, out_range, out_chroma, deliver, deliver_filter):
+    def __init__(self, device, render_hw, pix, out_pix_fmt, out_matrix, out_range, out_chroma, deliver, deliver_filter,
+                 deliver_fit="stretch", pad_color=(0, 0, 0)):
         self.device, self.pix = device, pix
         self.size = tuple(deliver) if deliver is not None else tuple(render_hw)
-        self.resize = resize_plan(device, render_hw, self.size, deliver_filter, pix) if deliver is not None else None
+        self.resize = self.canvas = None
+        self.stages = []                 # (plan, the size of the frames it writes), in order, in front of the egress plan
+        inner, at = fit_pad(render_hw, self.size) if deliver is not None and deliver_fit == "pad" else (self.size, (0, 0))
+        window = fit_crop(render_hw, self.size) if deliver is not None and deliver_fit == "crop" else (0, 0) + tuple(render_hw)
+        if inner != self.size:
+            if inner != tuple(render_hw):
+                self.resize = resize_plan(device, render_hw, inner, deliver_filter, pix)
+                self.stages.append((self.resize, inner))
+            self.canvas = Canvas(device, inner, self.size, at=at, fill=pad_color, dtype=pix)
+            self.stages.append((self.canvas, self.size))
+        elif window[2:] != tuple(render_hw):
+            self.canvas = Canvas(device, render_hw, window[2:], window=window, dtype=pix)
+            self.stages.append((self.canvas, window[2:]))
+            if window[2:] != self.size:
+                self.resize = resize_plan(device, window[2:], self.size, deliver_filter, pix)
+                self.stages.append((self.resize, self.size))
+        elif deliver is not None:
+            self.resize = resize_plan(device, render_hw, self.size, deliver_filter, pix)
+            self.stages.append((self.resize, self.size))
         self.egress = formats.egress_plan(device, self.size, out_pix_fmt, out_matrix, out_range, out_chroma)
         self.frame_bytes = self.size[0] * self.size[1] * 3 if self.egress is None else self.egress.frame_bytes
 
@@ -65,16 +96,18 @@ class DeliveryEnd:
         import torch
         B = int(dev_out[0].shape[0])
         self.out = self.fin = self.send = dev_out
-        if self.resize is not None:
-            self.fin = self.send = [torch.empty((B,) + self.size + (3,), dtype=self.pix, device=self.device) for _ in dev_out]
+        self.bufs = [[torch.empty((B,) + hw + (3,), dtype=self.pix, device=self.device) for _ in dev_out] for _, hw in self.stages]
+        if self.bufs:
+            self.fin = self.send = self.bufs[-1]
         if self.egress is not None:
             self.send = [torch.empty(self.shape(B), dtype=torch.uint8, device=self.device) for _ in dev_out]
         return self.fin, self.send
 
     def run(self, d: int, n: int):
         """Slot d's stages over its first n frames; returns the frames to download.  The caller has awaited the slot's last download."""
-        if self.resize is not None:
-            self.resize.run(self.out[d][:n], out=self.fin[d][:n])
+        x = self.out[d][:n]
+        for (stage, _), buf in zip(self.stages, self.bufs):
+            x = stage.run(x, out=buf[d][:n])
         if self.egress is not None:
             self.egress.run(self.fin[d][:n], out=self.send[d][:n])
         return self.send[d][:n]

@@ -95,6 +95,42 @@ def parse_deliver_size(deliver_size, out_h: int, out_w: int) -> Optional[Tuple[i
     return None if (dh, dw) == (int(out_h), int(out_w)) else (dh, dw)
 
 
+DELIVER_FITS = ("stretch", "pad", "crop")
+
+
+def parse_in_crop(in_crop, bounds: Optional[Tuple[int, int]] = None, name: str = "in_crop") -> Optional[Tuple[int, int, int, int]]:
+    """(y, x, h, w) of `process_frames(in_crop=)`, or None.  ValueError: not four integers, a side < 1, an origin < 0, and — where the
+    source size `bounds` = (src_h, src_w) is known — a window that leaves it."""
+    if in_crop is None:
+        return None
+    try:
+        vals = tuple(in_crop)
+        if len(vals) != 4 or any(isinstance(v, bool) or int(v) != v for v in vals):
+            raise TypeError
+        y, x, ch, cw = (int(v) for v in vals)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be four integers (y, x, height, width), got {in_crop!r}") from None
+    if min(ch, cw) < 1 or min(y, x) < 0:
+        raise ValueError(f"{name}={(y, x, ch, cw)}: a window needs an origin >= 0 and sides >= 1")
+    if bounds is not None and (y + ch > bounds[0] or x + cw > bounds[1]):
+        raise ValueError(f"{name}={(y, x, ch, cw)}: the window leaves the {bounds[0]} x {bounds[1]} source frame")
+    return y, x, ch, cw
+
+
+def parse_pad_color(color, name: str = "deliver_pad_color") -> Tuple[int, int, int]:
+    """(r, g, b) of `process_frames(deliver_pad_color=)`.  ValueError: not three integers 0..255."""
+    try:
+        vals = tuple(color)
+        if len(vals) != 3 or any(isinstance(v, bool) or int(v) != v for v in vals):
+            raise TypeError
+        vals = tuple(int(v) for v in vals)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be three integers (r, g, b) in 0..255, got {color!r}") from None
+    if min(vals) < 0 or max(vals) > 255:
+        raise ValueError(f"{name}={vals}: values outside 0..255")
+    return vals
+
+
 def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.ndarray], None], out_w: int, out_h: int, fps_out: float,
                    total_frames: Optional[int] = None, *,
                    scanline_strength: float = 0.6, triad_strength: float = 0.35, triad_gamma: float = 2.2, triad_preserve_luma: bool = False,
@@ -110,7 +146,8 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                    out_pix_fmt: str = "rgb24", out_matrix: str = "bt601", out_range: str = "tv",
                    in_pix_fmt: str = "rgb24", in_matrix: str = "bt601", in_range: str = "tv", in_size: Optional[Tuple[int, int]] = None,
                    in_chroma: str = "replicate", out_chroma: str = "center", deliver_size: Optional[Tuple[int, int]] = None,
-                   in_filter: str = "bilinear", deliver_filter: str = "bilinear", **io_keywords) -> int:
+                   in_filter: str = "bilinear", deliver_filter: str = "bilinear", in_crop: Optional[Tuple[int, int, int, int]] = None,
+                   deliver_fit: str = "stretch", deliver_pad_color: Tuple[int, int, int] = (0, 0, 0), **io_keywords) -> int:
     """Render every frame of `frame_iter` (H x W x 3 uint8 RGB arrays) and hand the finished uint8 frames to `write_frame` in order.
     Effect keywords: the names, meaning and defaults of process_video / the CLI (ref:864-911, :1155-1206); the caller applies the clamps of
     ref:1225-1266 as the reference's `main` does (`pythoncrt_amd.cli.settings_from_args` restates them).  Returns the number of frames written.
@@ -174,6 +211,19 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     `Image.resize(size, filter)` gives them, and `resize_on="host"` hands `in_filter` to Pillow itself (the same bytes).  Refused with
     ValueError before a device is touched: an unknown name, and a `deliver_filter` other than "bilinear" without a `deliver_size` that
     differs from the render size (there is nothing to filter).
+    `in_crop=(y, x, h, w)` cuts that window out of every source frame on the device before anything else sees it (a letterboxed film: the
+    picture area, not the bars, fills the tube): Canvas (include/crtfx_canvas.h) stands behind the source plan and in front of the resize
+    that brings the window to the render size.  With a packed `in_pix_fmt` it is a window of the `in_size` frame (of the render size
+    without one); with "rgb24" a window of every frame at that frame's own size — a frame of the render size goes through it too — and a
+    frame too small for it raises ValueError.  A 10-bit input may be cropped where the window has the render size (the Canvas then moves
+    half pixels); any other window would have to be resized and is refused as `in_size` is.
+    `deliver_fit` says how a render meets a `deliver_size` of another aspect: "stretch" (default) is the path as it was; "pad" resizes the
+    render to the largest size of its own aspect inside the delivery (canvas.fit_pad) and centres it on a frame of `deliver_pad_color`
+    (r, g, b in 0..255; a 4:3 render pillarboxed in 16:9); "crop" cuts the largest centred window of the delivery's aspect out of the
+    render (canvas.fit_crop) and resizes that.  Where the aspects agree no Canvas is created and the bytes are those of "stretch".
+    Refused with ValueError before a device is touched: an `in_crop` that is not four integers, has a side < 1 or leaves `in_size`;
+    `in_crop` with `resize_on="host"`; an unknown `deliver_fit`; a `deliver_fit` other than "stretch" without a `deliver_size` that
+    differs from the render size (there is nothing to fit); a pad colour outside 0..255.
     If `frame_iter` or `write_frame` raises, the GPU work already queued is drained (device synchronize) before the exception leaves this
     function, so that the staging buffers are not freed under a running copy."""
     import os
@@ -201,11 +251,20 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     if out_chroma != "center" and out_pix_fmt not in sited.LAYOUTS:
         raise ValueError(f"out_chroma={out_chroma!r} with out_pix_fmt={out_pix_fmt!r}: only a 4:2:0 or 4:2:2 output has chroma to "
                          f"down-sample ({', '.join(sited.LAYOUTS)})")
+    crop = parse_in_crop(in_crop, None if in_pix_fmt == "rgb24" else ((int(out_h), int(out_w)) if in_size is None else (int(in_size[0]), int(in_size[1]))))
+    if crop is not None and resize_on == "host":
+        raise ValueError(f"resize_on='host' cannot be combined with in_crop={crop}: the window is cut on the device")
+    if deliver_fit not in DELIVER_FITS:
+        raise ValueError(f"deliver_fit must be one of {', '.join(DELIVER_FITS)}, got {deliver_fit!r}")
+    pad_color = parse_pad_color(deliver_pad_color)
     deep = formats.bits(in_pix_fmt) == 10                                      # both ends or neither
     if deep != (formats.bits(out_pix_fmt) == 10):
         raise ValueError(f"in_pix_fmt={in_pix_fmt!r} with out_pix_fmt={out_pix_fmt!r}: a 10-bit format on one end only — the chain between "
                          "them runs on half pixels or on uint8 ones, and the 8-bit stages have no half path (the 10-bit ones no uint8 path)")
-    if deep and in_size is not None and (int(in_size[0]), int(in_size[1])) != (int(out_h), int(out_w)):
+    if deep and crop is not None and crop[2:] != (int(out_h), int(out_w)):
+        raise ValueError(f"in_crop={crop} leaves a {crop[2]} x {crop[3]} window that differs from the output size {(int(out_h), int(out_w))}: a "
+                         "10-bit input cannot be resized (IngestResize has no half path)")
+    if deep and crop is None and in_size is not None and (int(in_size[0]), int(in_size[1])) != (int(out_h), int(out_w)):
         raise ValueError(f"in_size={tuple(in_size)} differs from the output size {(int(out_h), int(out_w))}: a 10-bit input cannot be "
                          "resized (IngestResize has no half path)")
     if in_pix_fmt != "rgb24" and resize_on == "host":
@@ -217,6 +276,8 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     if deliver_filter != "bilinear" and deliver is None:
         raise ValueError(f"deliver_filter={deliver_filter!r} without a deliver_size that differs from the render size: there is no delivery "
                          "resize to filter")
+    if deliver_fit != "stretch" and deliver is None:
+        raise ValueError(f"deliver_fit={deliver_fit!r} without a deliver_size that differs from the render size: there is nothing to fit")
     if not torch.cuda.is_available():
         raise RuntimeError("no ROCm device visible; pythoncrt_amd has no CPU fallback")
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -242,7 +303,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
 
     NS = 2
     pin_in = [torch.empty((B, h, w, 3), dtype=torch.uint8).pin_memory() for _ in range(NS)] if in_pix_fmt == "rgb24" else None   # else: a SourceEnd's own
-    end =DeliveryEnd(dev, (h, w), pix, out_pix_fmt, out_matrix, out_range, out_chroma, deliver, deliver_filter)
+    end = DeliveryEnd(dev, (h, w), pix, out_pix_fmt, out_matrix, out_range, out_chroma, deliver, deliver_filter, deliver_fit, pad_color)
     pin_out = [torch.empty(end.shape(B), dtype=torch.uint8).pin_memory() for _ in range(NS)]    # what is downloaded and handed to the writer
     dev_in = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]
     dev_out = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]
@@ -269,7 +330,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                 torch.cuda.synchronize(dev)
                 sources.pop(next(iter(sources)))
             fmt, hw = (in_pix_fmt, yuv_hw) if key == YUV else ("rgb24", key)
-            src = SourceEnd(dev, (h, w), fmt, in_matrix, in_range, in_chroma, hw, in_filter).slots(B, NS)
+            src = SourceEnd(dev, (h, w), fmt, in_matrix, in_range, in_chroma, hw, in_filter, crop, pix).slots(B, NS)
             assert key != YUV or src.frame_bytes == yuv_bytes
         sources[key] = src
         return src
@@ -286,6 +347,10 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
             return a, YUV
         if a.ndim != 3 or a.shape[2] != 3:
             raise ValueError(f"frames must be H x W x 3 RGB arrays, got {a.shape}")
+        if crop is not None:                                                    # every frame goes through a SourceEnd of ITS size
+            if a.shape[0] < crop[0] + crop[2] or a.shape[1] < crop[1] + crop[3]:
+                raise ValueError(f"in_crop={crop}: the window leaves a frame of {a.shape[0]} x {a.shape[1]}")
+            return a, (int(a.shape[0]), int(a.shape[1]))
         if a.shape[0] != h or a.shape[1] != w:                                  # ref:1039-1041
             if resize_on == "device":
                 return a, (int(a.shape[0]), int(a.shape[1]))

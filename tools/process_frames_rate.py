@@ -6,7 +6,9 @@ PCIe both ways, the per-frame write_frame call).
     python tools/process_frames_rate.py --size 2160x3840 --source 1080x1920       # a 1080p source rendered at 4K (resized on the device)
     python tools/process_frames_rate.py --size 2160x3840 --source 1080x1920 --resize-on host --frames 48     # ... by Pillow on the host
     python tools/process_frames_rate.py --size 2160x3840 --out-pix-fmt yuv420p --deliver 1080x1920            # a 4K render delivered as 1080p yuv420p
-    options: --frames N (per repeat), --repeats R, --chain full|default|both, --out-pix-fmt FMT, --deliver HxW (process_frames(deliver_size=))"""
+    python tools/process_frames_rate.py --size 2160x2880 --out-pix-fmt yuv420p --deliver 1080x1920 --deliver-fit pad  # a 4:3 render pillarboxed in 1080p
+    options: --frames N (per repeat), --repeats R, --chain full|default|both, --out-pix-fmt FMT, --deliver HxW (process_frames(deliver_size=)),
+             --deliver-fit stretch|pad|crop (process_frames(deliver_fit=))"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -33,6 +35,8 @@ if opt("--out-pix-fmt"):
     extra["out_pix_fmt"] = opt("--out-pix-fmt")
 if opt("--deliver"):
     extra["deliver_size"] = hw(opt("--deliver"))
+if opt("--deliver-fit"):
+    extra["deliver_fit"] = opt("--deliver-fit")
 for (h, w, n) in sizes:
     sh, sw = hw(source) if source else (h, w)
     rng = np.random.default_rng(0)
@@ -46,5 +50,5 @@ for (h, w, n) in sizes:
             src = "" if (sh, sw) == (h, w) else f" from a {sw}x{sh} source (resize_on={resize_on or 'default'})"
             if "deliver_size" in extra or "out_pix_fmt" in extra:
                 dh, dw = extra.get("deliver_size", (h, w))
-                src += f" written as {dw}x{dh} {extra.get('out_pix_fmt', 'rgb24')}"
+                src += f" written as {dw}x{dh} {extra.get('out_pix_fmt', 'rgb24')}" + (f" (deliver_fit={extra['deliver_fit']})" if "deliver_fit" in extra else "")
             print(f"{w}x{h}{src} {name}: {k} frames in {dt:.3f} s = {k / dt:.0f} frames/s (set-up of the call included)", flush=True)
