@@ -64,6 +64,18 @@ chroma_location=left (or nothing) and the only siting 4:2:2 defines; pass `-chro
 centres the render, resized to fit, on a frame of `--deliver-pad-color` (a 4:3 render pillarboxed in 16:9) and `--deliver-fit crop` cuts the
 centred window of the delivery's aspect; the default `stretch` is the path as it was.
 
+`--chain-pix half` runs the chain on half pixels whatever the formats (include/crtfx_depth.h), so the two ends need not have the same
+depth — a 10-bit master delivered as 8-bit 4:2:0, no host `format=` filter around the tool:
+
+    ffmpeg -i prores.mov -f rawvideo -pix_fmt p010le - |
+      python -m pythoncrt_amd.cli --input - --width 1920 --height 1080 --fps 24 --output - --in-pix-fmt p010le --out-pix-fmt yuv420p \
+             --chain-pix half --dither ordered [effect flags] |
+      ffmpeg -f rawvideo -pix_fmt yuv420p -s 1920x1080 -r 24 -i - out.mp4
+
+An 8-bit source is widened to half behind its own uint8 stages, an 8-bit delivery is narrowed at the delivery size behind the half
+geometry, and `--dither ordered` adds an 8 x 8 Bayer threshold there instead of rounding to nearest (`none`, the default).  The default
+`--chain-pix auto` is the path as it was, the one-end refusal included; `--dither ordered` needs `--chain-pix half` and an 8-bit output.
+
 `--gui`, `--gpu`, `--nvenc-preset`, `--encoder`, `--decoder`, `--crf` and `--bitrate` are accepted for
 compatibility and ignored (encode/decode/UI are not part of this path).  `--text*` rasterise the overlay on
 the host with Pillow (ref:366-414) and alpha-blend it on the GPU before or after the effects.
@@ -187,6 +199,13 @@ def add_output_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
                         "inside and centre it on a frame of --deliver-pad-color (a 4:3 render pillarboxed in 16:9), or crop: cut the centred window "
                         "of the delivery's aspect and resize that; on the GPU (include/crtfx_canvas.h); needs a delivery size other than the render size")
     p.add_argument("--deliver-pad-color", type=str, default="0,0,0", help="R,G,B of the bars of --deliver-fit pad, each 0..255 (default 0,0,0)")
+    p.add_argument("--chain-pix", type=str, default="auto", choices=["auto", "half"],
+                   help="what the chain runs on: what the formats say (auto, default: uint8 pixels, or half ones between two 10-bit formats), or half "
+                        "pixels whatever the formats (half): an 8-bit input is widened and an 8-bit output narrowed on the GPU "
+                        "(include/crtfx_depth.h), so a 10-bit format may stand on one end only")
+    p.add_argument("--dither", type=str, default="none", choices=["none", "ordered"],
+                   help="how --chain-pix half narrows its half frames to an 8-bit output: round to nearest (none, default) or 8 x 8 ordered (Bayer) "
+                        "dither at the delivered frame's coordinates (ordered); needs --chain-pix half and an 8-bit or rgb24 --out-pix-fmt")
     return p
 
 
@@ -311,6 +330,9 @@ def main_sharded(a, rank: int, world: int) -> int:
     the clip's chunks of --batch frames are dealt round-robin over the ranks, each rank reads its chunks
     from the raw input file and writes them at the same offsets of the output file; with --persistence > 0 one
     float32 state frame per chunk boundary travels to the next rank (RCCL)."""
+    if getattr(a, "chain_pix", "auto") != "auto":
+        raise SystemExit(f"--chain-pix {a.chain_pix} (and with it --dither) is not supported by the sharded CLI (one process per GPU reads and writes "
+                         "rgb24 on a uint8 chain); run one process")
     if getattr(a, "deliver_width", 0) or getattr(a, "deliver_height", 0):
         # every rank writes its chunks at offsets of its own: those, and the downloads behind them, are at render size here
         raise SystemExit("--deliver-width / --deliver-height are not supported by the sharded CLI (one process per GPU writes rgb24 at render size); "
@@ -460,13 +482,19 @@ def main_sharded(a, rank: int, world: int) -> int:
 
 
 def check_flags(a):
-    """Every refusal from the flags alone, before torch, a device or the output file.  -> delivery size | None, half chain?, (rank, world) | None."""
+    """Every refusal from the flags alone, before torch, a device or the output file.  -> delivery size | None, half chain (10-bit formats on
+    both ends, or --chain-pix half)?, (rank, world) | None."""
     if a.in_chroma != "replicate" and a.in_pix_fmt not in sited.LAYOUTS:
         raise SystemExit(f"--in-chroma {a.in_chroma} with --in-pix-fmt {a.in_pix_fmt}: only a 4:2:0 or 4:2:2 input has sub-sampled chroma to interpolate "
                          f"({', '.join(sited.LAYOUTS)})")
     if a.out_chroma != "center" and a.out_pix_fmt not in sited.LAYOUTS:
         raise SystemExit(f"--out-chroma {a.out_chroma} with --out-pix-fmt {a.out_pix_fmt}: only a 4:2:0 or 4:2:2 output has chroma to down-sample "
                          f"({', '.join(sited.LAYOUTS)})")
+    half = getattr(a, "chain_pix", "auto") == "half"
+    deep, deep_out = formats.bits(a.in_pix_fmt) == 10, formats.bits(a.out_pix_fmt) == 10
+    if getattr(a, "dither", "none") != "none" and (not half or deep_out):
+        raise SystemExit(f"--dither {a.dither} with --chain-pix {getattr(a, 'chain_pix', 'auto')} and --out-pix-fmt {a.out_pix_fmt}: only half frames "
+                         "narrowed to an 8-bit output are dithered; pass --chain-pix half and an 8-bit or rgb24 --out-pix-fmt")
     deliver = deliver_size_from_args(a)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("CRTFX_FORCE_DIST") == "1":
         if a.gui or not a.input or a.width <= 0 or a.height <= 0:
@@ -478,8 +506,7 @@ def check_flags(a):
         raise SystemExit("the GUI is not part of this path; pass --input (raw rgb24 / yuv420p / nv12 / yuv422p / yuyv422 / uyvy422 / yuv420p10le / p010le / yuv444p10le / gbrp10le / x2rgb10le file or '-')")
     if a.width <= 0 or a.height <= 0:
         raise SystemExit("raw input needs --width and --height")
-    deep = formats.bits(a.in_pix_fmt) == 10
-    if deep != (formats.bits(a.out_pix_fmt) == 10):
+    if not half and deep != deep_out:
         raise SystemExit(f"--in-pix-fmt {a.in_pix_fmt} with --out-pix-fmt {a.out_pix_fmt}: a 10-bit format on one end only; the chain between them "
                          "runs on half pixels or on uint8 ones — pass yuv420p10le / p010le (or yuv444p10le / gbrp10le / x2rgb10le) on both ends "
                          "or on neither")
@@ -487,7 +514,7 @@ def check_flags(a):
     if deep and crop is not None and crop[2:] != (int(a.height), int(a.width)):
         raise SystemExit(f"--in-crop-width {crop[3]} --in-crop-height {crop[2]} differs from --width {a.width} x --height {a.height}: a 10-bit input "
                          "cannot be resized (IngestResize has no half path)")
-    return deliver, deep, None
+    return deliver, deep or half, None
 
 
 def open_output(a, fin, out_path: str, B: int, in_bytes: int, out_bytes: int):
@@ -649,7 +676,7 @@ def main(argv=None) -> int:
         return main_sharded(a, *ranks)
     t_start = time.perf_counter()
     import torch
-    from .ends import DeliveryEnd, SourceEnd
+    from .ends import DeliveryEnd, SourceEnd, depth_stages
     from .pipeline import FramePipeline
     from .staging import _Reader, _Writer
     from .text import make_text_overlay_rgba
@@ -662,16 +689,19 @@ def main(argv=None) -> int:
     dev = torch.device("cuda", torch.cuda.current_device())
     seed = a.noise_seed if a.noise_seed is not None else int.from_bytes(os.urandom(8), "little")
     overlay = make_text_overlay_rgba(w, h, a.text, a.text_font, a.text_size, a.text_color, (a.text_x, a.text_y)) if a.text else None   # ref:1076
-    pix = torch.float16 if deep else torch.uint8                   # 10-bit formats on both ends: the chain runs on half pixels (include/crtfx_deep.h, crtfx_444.h)
+    pix = torch.float16 if deep else torch.uint8                   # 10-bit formats on both ends, or --chain-pix half: the chain runs on half pixels
+    # --chain-pix half: uint8 stages in front of the chain end in a Widen, a Narrow stands in front of the 8-bit egress plan (include/crtfx_depth.h)
+    _, widen, narrow = depth_stages(a.in_pix_fmt, a.out_pix_fmt, a.chain_pix, a.dither)
     pipe = FramePipeline(dev, h, w, rs, fps=fps_out, noise_seed=seed, dtype=pix, text_overlay_rgba=overlay, text_overlay_after=bool(a.text_after))
     t_engine = time.perf_counter() - t_start - t_imports
     fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb", buffering=0)
     out_path = a.output if a.output else (a.input + "_crt.rgb" if a.input != "-" else "-")
     B, NS = max(1, int(a.batch)), 3
-    end = DeliveryEnd(dev, (h, w), pix, a.out_pix_fmt, a.out_matrix, a.out_range, a.out_chroma, deliver, a.deliver_filter, a.deliver_fit, pad_color_from_args(a))
+    end = DeliveryEnd(dev, (h, w), pix, a.out_pix_fmt, a.out_matrix, a.out_range, a.out_chroma, deliver, a.deliver_filter, a.deliver_fit, pad_color_from_args(a),
+                      narrow=narrow)
     crop = in_crop_from_args(a)                                    # a window of the input: an rgb24 input then has a source end too
-    source = (SourceEnd(dev, (h, w), a.in_pix_fmt, a.in_matrix, a.in_range, a.in_chroma, (h, w), a.in_filter, crop, pix)
-              if a.in_pix_fmt != "rgb24" or crop is not None else None)
+    source = (SourceEnd(dev, (h, w), a.in_pix_fmt, a.in_matrix, a.in_range, a.in_chroma, (h, w), a.in_filter, crop, pix, widen=widen)
+              if a.in_pix_fmt != "rgb24" or crop is not None or widen else None)    # half chain: an rgb24 input goes through a Widen
     in_bytes = h * w * 3 if source is None else source.frame_bytes
     t0 = time.perf_counter()
     fout, in_pos, out_pos, pipes, out_plan = open_output(a, fin, out_path, B, in_bytes, end.frame_bytes)

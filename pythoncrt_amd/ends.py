@@ -3,6 +3,15 @@
 from . import formats
 from ._stage import resize_plan
 from .canvas import Canvas, fit_crop, fit_pad
+from .depth import Narrow, Widen
+
+
+def depth_stages(in_pix_fmt: str, out_pix_fmt: str, chain_pix: str = "auto", dither: str = "none"):
+    """(half, widen, narrow) for a pair of formats the caller has admitted: does the chain run on half pixels, does a Widen stand behind
+    the source's uint8 stages, and the dither of the Narrow in front of the 8-bit delivery (None: there is none).  Under "auto" the chain
+    is half between two 10-bit ends and neither depth stage exists; under "half" every 8-bit (or rgb24) end gets its depth stage."""
+    deep_in, deep_out, forced = formats.bits(in_pix_fmt) == 10, formats.bits(out_pix_fmt) == 10, chain_pix == "half"
+    return forced or (deep_in and deep_out), forced and not deep_in, dither if forced and not deep_out else None
 
 
 class StagingSlots:
@@ -23,22 +32,26 @@ class StagingSlots:
 class SourceEnd(StagingSlots):
     """Frames of `in_pix_fmt` at `src_hw`, staged at THEIR size: [source plan] (none for rgb24), RGB slots of src_hw, [Canvas cutting the
     window `crop` = (y, x, ch, cw) of the source frame], [resize of what is left to the render size] (ref:1039-1041).  The RGB side of the
-    source plan, the window and the resize are frames of `dtype`."""
+    source plan, the window and the resize are frames of `dtype`.  With `widen` those are uint8 frames in front of a half chain: a Widen at
+    the render size (include/crtfx_depth.h) is then the last stage and writes the chain's half input — for an rgb24 frame at render size
+    the only one."""
 
-    def __init__(self, device, render_hw, in_pix_fmt, in_matrix, in_range, in_chroma, src_hw, in_filter, crop=None, dtype=None):
+    def __init__(self, device, render_hw, in_pix_fmt, in_matrix, in_range, in_chroma, src_hw, in_filter, crop=None, dtype=None, widen=False):
         import torch
         self.device, self.src_hw = device, tuple(src_hw)
-        self.dtype = torch.uint8 if dtype is None else dtype
+        self.dtype = torch.uint8 if dtype is None or widen else dtype      # widen: `dtype` is the chain's, the stages in front of it run on uint8
         self.plan = formats.source_plan(device, self.src_hw, in_pix_fmt, in_matrix, in_range, in_chroma)
         self.canvas, cut = None, self.src_hw
         if crop is not None:
             cut = (int(crop[2]), int(crop[3]))
             self.canvas = Canvas(device, self.src_hw, cut, window=tuple(int(v) for v in crop), dtype=self.dtype)
         self.resize = resize_plan(device, cut, render_hw, in_filter, self.dtype) if cut != tuple(render_hw) else None
+        self.widen = Widen(device, tuple(render_hw)) if widen else None
         self.frame_bytes = formats.frame_bytes(*self.src_hw, in_pix_fmt) if self.plan is None else self.plan.frame_bytes
         self.frame_shape = self.src_hw + (3,) if self.plan is None else (self.frame_bytes,)
         # the stages present, each with the size of the RGB frames it writes; the last one writes the chain's input
-        self.stages = [(st, hw) for st, hw in ((self.plan, self.src_hw), (self.canvas, cut), (self.resize, tuple(render_hw))) if st is not None]
+        self.stages = [(st, hw) for st, hw in ((self.plan, self.src_hw), (self.canvas, cut), (self.resize, tuple(render_hw)),
+                                                    (self.widen, tuple(render_hw))) if st is not None]
 
     def slots(self, B: int, NS: int, pinned: bool = True):
         import torch
@@ -60,13 +73,16 @@ class DeliveryEnd:
     meets the delivery: "stretch" resizes it to (dh, dw); "pad" resizes it to fit_pad's inner size (no resize where that is the render
     size) and a Canvas centres that on a (dh, dw) frame of `pad_color`; "crop" has a Canvas cut fit_crop's window and resizes that to
     (dh, dw) (no resize where the window has that size).  Where the aspects agree — inner = delivery, window = the whole render — no
-    Canvas is built and the stages are those of "stretch".  Everything downstream is in frames of `frame_bytes`, batches of `shape(B)`."""
+    Canvas is built and the stages are those of "stretch".  `narrow` is None or a dither name of depth.DITHERS: the chain runs on half
+    pixels and the delivery is an 8-bit one, so behind the geometry, which runs on the half frames, a Narrow at the delivery size
+    (include/crtfx_depth.h) writes the uint8 frames the egress plan reads — or, for "rgb24", the frames that are downloaded; the dither's
+    coordinates are those of the delivered frame.  Everything downstream is in frames of `frame_bytes`, batches of `shape(B)`."""
 
     def __init__(self, device, render_hw, pix, out_pix_fmt, out_matrix, out_range, out_chroma, deliver, deliver_filter,
-                 deliver_fit="stretch", pad_color=(0, 0, 0)):
+                 deliver_fit="stretch", pad_color=(0, 0, 0), narrow=None):
         self.device, self.pix = device, pix
         self.size = tuple(deliver) if deliver is not None else tuple(render_hw)
-        self.resize = self.canvas = None
+        self.resize = self.canvas = self.narrow = None
         self.stages = []                 # (plan, the size of the frames it writes), in order, in front of the egress plan
         inner, at = fit_pad(render_hw, self.size) if deliver is not None and deliver_fit == "pad" else (self.size, (0, 0))
         window = fit_crop(render_hw, self.size) if deliver is not None and deliver_fit == "crop" else (0, 0) + tuple(render_hw)
@@ -85,6 +101,9 @@ class DeliveryEnd:
         elif deliver is not None:
             self.resize = resize_plan(device, render_hw, self.size, deliver_filter, pix)
             self.stages.append((self.resize, self.size))
+        if narrow is not None:
+            self.narrow = Narrow(device, self.size, dither=narrow)
+            self.stages.append((self.narrow, self.size))
         self.egress = formats.egress_plan(device, self.size, out_pix_fmt, out_matrix, out_range, out_chroma)
         self.frame_bytes = self.size[0] * self.size[1] * 3 if self.egress is None else self.egress.frame_bytes
 
@@ -96,7 +115,8 @@ class DeliveryEnd:
         import torch
         B = int(dev_out[0].shape[0])
         self.out = self.fin = self.send = dev_out
-        self.bufs = [[torch.empty((B,) + hw + (3,), dtype=self.pix, device=self.device) for _ in dev_out] for _, hw in self.stages]
+        self.bufs = [[torch.empty((B,) + hw + (3,), dtype=torch.uint8 if st is self.narrow else self.pix, device=self.device) for _ in dev_out]
+                     for st, hw in self.stages]
         if self.bufs:
             self.fin = self.send = self.bufs[-1]
         if self.egress is not None:

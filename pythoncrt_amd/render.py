@@ -96,6 +96,7 @@ def parse_deliver_size(deliver_size, out_h: int, out_w: int) -> Optional[Tuple[i
 
 
 DELIVER_FITS = ("stretch", "pad", "crop")
+CHAIN_PIX = ("auto", "half")        # what the chain runs on: what the formats say (uint8, or half between two 10-bit ends), or half whatever they are
 
 
 def parse_in_crop(in_crop, bounds: Optional[Tuple[int, int]] = None, name: str = "in_crop") -> Optional[Tuple[int, int, int, int]]:
@@ -147,7 +148,8 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                    in_pix_fmt: str = "rgb24", in_matrix: str = "bt601", in_range: str = "tv", in_size: Optional[Tuple[int, int]] = None,
                    in_chroma: str = "replicate", out_chroma: str = "center", deliver_size: Optional[Tuple[int, int]] = None,
                    in_filter: str = "bilinear", deliver_filter: str = "bilinear", in_crop: Optional[Tuple[int, int, int, int]] = None,
-                   deliver_fit: str = "stretch", deliver_pad_color: Tuple[int, int, int] = (0, 0, 0), **io_keywords) -> int:
+                   deliver_fit: str = "stretch", deliver_pad_color: Tuple[int, int, int] = (0, 0, 0), chain_pix: str = "auto",
+                   dither: str = "none", **io_keywords) -> int:
     """Render every frame of `frame_iter` (H x W x 3 uint8 RGB arrays) and hand the finished uint8 frames to `write_frame` in order.
     Effect keywords: the names, meaning and defaults of process_video / the CLI (ref:864-911, :1155-1206); the caller applies the clamps of
     ref:1225-1266 as the reference's `main` does (`pythoncrt_amd.cli.settings_from_args` restates them).  Returns the number of frames written.
@@ -224,12 +226,25 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     Refused with ValueError before a device is touched: an `in_crop` that is not four integers, has a side < 1 or leaves `in_size`;
     `in_crop` with `resize_on="host"`; an unknown `deliver_fit`; a `deliver_fit` other than "stretch" without a `deliver_size` that
     differs from the render size (there is nothing to fit); a pad colour outside 0..255.
+    `chain_pix="half"` runs the chain on half pixels (FramePipeline(dtype=torch.float16)) whatever the formats, so the two ends need not
+    have the same depth: a 10-bit master is delivered as "yuv420p" / "nv12", an 8-bit source is written as a 10-bit mezzanine, and an
+    8-bit job gets the half chain, which rounds to 8 bits once, at the very end.  An 8-bit or "rgb24" source keeps its uint8 stages
+    (source plan, Canvas, resize) and a Widen (include/crtfx_depth.h: half(u), exact) writes the chain's input behind them — an rgb24 frame
+    at render size goes through a source end whose only stage is that Widen; an 8-bit or "rgb24" delivery runs its geometry (resize,
+    Canvas) on the half frames, a Narrow at the delivery size turns them into uint8 frames, and the 8-bit egress plan reads those (for
+    "rgb24" they are what is downloaded).  `dither` is that Narrow's rounding: "none" (default) rounds to nearest, ties to even, as the
+    uint8 chain's quantiser does; "ordered" adds the 8 x 8 Bayer threshold of the pixel's place in the delivered frame before the floor,
+    one threshold for the three channels, which breaks up the banding of smooth dark ramps (vignette, bloom).  A 10-bit end is as it was,
+    with its refusals (`in_size`, a crop that needs a resize); with 10-bit formats on both ends "half" builds no depth plan and gives the
+    bytes of "auto".  "auto" (default) is the path as it was, the one-end refusal included.  Refused with ValueError before a device is
+    touched: an unknown `chain_pix` or `dither`; `dither` other than "none" where no Narrow would stand (`chain_pix="auto"`, or a 10-bit
+    `out_pix_fmt`).
     If `frame_iter` or `write_frame` raises, the GPU work already queued is drained (device synchronize) before the exception leaves this
     function, so that the staging buffers are not freed under a running copy."""
     import os
     import torch
     from .pipeline import FramePipeline, RenderSettings
-    from .ends import DeliveryEnd, SourceEnd, StagingSlots
+    from .ends import DeliveryEnd, SourceEnd, StagingSlots, depth_stages
     unknown = set(io_keywords) - set(_IO_KEYS)
     if unknown:
         raise TypeError(f"process_frames() got unexpected keyword arguments {sorted(unknown)}")
@@ -257,8 +272,17 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     if deliver_fit not in DELIVER_FITS:
         raise ValueError(f"deliver_fit must be one of {', '.join(DELIVER_FITS)}, got {deliver_fit!r}")
     pad_color = parse_pad_color(deliver_pad_color)
-    deep = formats.bits(in_pix_fmt) == 10                                      # both ends or neither
-    if deep != (formats.bits(out_pix_fmt) == 10):
+    from .depth import DITHERS
+    if chain_pix not in CHAIN_PIX:
+        raise ValueError(f"chain_pix must be one of {', '.join(CHAIN_PIX)}, got {chain_pix!r} (dither={dither!r})")
+    if dither not in DITHERS:
+        raise ValueError(f"dither must be one of {', '.join(DITHERS)}, got {dither!r} (chain_pix={chain_pix!r})")
+    half = chain_pix == "half"
+    deep, deep_out = formats.bits(in_pix_fmt) == 10, formats.bits(out_pix_fmt) == 10       # under "auto": both ends or neither
+    if dither != "none" and (not half or deep_out):
+        raise ValueError(f"dither={dither!r} with chain_pix={chain_pix!r} and out_pix_fmt={out_pix_fmt!r}: only half frames narrowed to an 8-bit "
+                         "delivery are dithered (chain_pix='half' and an 8-bit or rgb24 out_pix_fmt)")
+    if not half and deep != deep_out:
         raise ValueError(f"in_pix_fmt={in_pix_fmt!r} with out_pix_fmt={out_pix_fmt!r}: a 10-bit format on one end only — the chain between "
                          "them runs on half pixels or on uint8 ones, and the 8-bit stages have no half path (the 10-bit ones no uint8 path)")
     if deep and crop is not None and crop[2:] != (int(out_h), int(out_w)):
@@ -297,13 +321,15 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         from .text import make_text_overlay_rgba
         overlay = make_text_overlay_rgba(w, h, text, text_font, int(text_size), text_color, tuple(text_pos))
     seed = int(noise_seed) if noise_seed is not None else int.from_bytes(os.urandom(8), "little")
-    pix = torch.float16 if deep else torch.uint8                               # what the chain runs on
+    on_half, widen, narrow = depth_stages(in_pix_fmt, out_pix_fmt, chain_pix, dither)      # widen: uint8 stages in front of a half chain end in a Widen
+    pix = torch.float16 if on_half else torch.uint8                            # what the chain runs on
     pipe = FramePipeline(dev, h, w, rs, fps=float(fps_out), noise_seed=seed, dtype=pix, text_overlay_rgba=overlay, text_overlay_after=bool(text_after))
     total = max(1, int(total_frames)) if total_frames else None
 
     NS = 2
-    pin_in = [torch.empty((B, h, w, 3), dtype=torch.uint8).pin_memory() for _ in range(NS)] if in_pix_fmt == "rgb24" else None   # else: a SourceEnd's own
-    end = DeliveryEnd(dev, (h, w), pix, out_pix_fmt, out_matrix, out_range, out_chroma, deliver, deliver_filter, deliver_fit, pad_color)
+    pin_in = [torch.empty((B, h, w, 3), dtype=torch.uint8).pin_memory() for _ in range(NS)] if in_pix_fmt == "rgb24" and not widen else None   # else: a SourceEnd's own
+    end = DeliveryEnd(dev, (h, w), pix, out_pix_fmt, out_matrix, out_range, out_chroma, deliver, deliver_filter, deliver_fit, pad_color,
+                      narrow=narrow)
     pin_out = [torch.empty(end.shape(B), dtype=torch.uint8).pin_memory() for _ in range(NS)]    # what is downloaded and handed to the writer
     dev_in = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]
     dev_out = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]
@@ -330,7 +356,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                 torch.cuda.synchronize(dev)
                 sources.pop(next(iter(sources)))
             fmt, hw = (in_pix_fmt, yuv_hw) if key == YUV else ("rgb24", key)
-            src = SourceEnd(dev, (h, w), fmt, in_matrix, in_range, in_chroma, hw, in_filter, crop, pix).slots(B, NS)
+            src = SourceEnd(dev, (h, w), fmt, in_matrix, in_range, in_chroma, hw, in_filter, crop, pix, widen=widen).slots(B, NS)
             assert key != YUV or src.frame_bytes == yuv_bytes
         sources[key] = src
         return src
@@ -356,7 +382,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                 return a, (int(a.shape[0]), int(a.shape[1]))
             from PIL import Image
             a = np.asarray(Image.fromarray(np.ascontiguousarray(a, dtype=np.uint8)).resize((w, h), getattr(Image, in_filter.upper())))
-        return a, None
+        return a, ((h, w) if widen else None)                                   # a half chain: no direct upload, the frame goes through a Widen
 
     def drain(p):
         nonlocal written
