@@ -76,6 +76,16 @@ An 8-bit source is widened to half behind its own uint8 stages, an 8-bit deliver
 geometry, and `--dither ordered` adds an 8 x 8 Bayer threshold there instead of rounding to nearest (`none`, the default).  The default
 `--chain-pix auto` is the path as it was, the one-end refusal included; `--dither ordered` needs `--chain-pix half` and an 8-bit output.
 
+`--deinterlace linear|edge` takes every input frame as two woven fields and deinterlaces it on the GPU before anything else sees it
+(include/crtfx_deint.h), `--field-order tff|bff` says which field comes first, and `--deinterlace-fields both` writes one frame per FIELD:
+the chain then runs at field rate and `--persistence` decays field to field, as phosphor does.  Pass the field rate as `--fps`; the output
+holds twice the input's frames.  A 480i uyvy422 capture sent as fields, no host `yadif` in front of the tool:
+
+    ffmpeg -i capture_480i.avi -f rawvideo -pix_fmt uyvy422 - |
+      python -m pythoncrt_amd.cli --input - --width 720 --height 480 --fps 60 --output - --in-pix-fmt uyvy422 \
+             --deinterlace edge --field-order bff --deinterlace-fields both [effect flags] |
+      ffmpeg -f rawvideo -pix_fmt rgb24 -s 720x480 -r 60000/1001 -i - out.mp4
+
 `--gui`, `--gpu`, `--nvenc-preset`, `--encoder`, `--decoder`, `--crf` and `--bitrate` are accepted for
 compatibility and ignored (encode/decode/UI are not part of this path).  `--text*` rasterise the overlay on
 the host with Pillow (ref:366-414) and alpha-blend it on the GPU before or after the effects.
@@ -286,7 +296,26 @@ def add_input_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--in-crop-y", type=int, default=0, help="top row of the window (see --in-crop-x)")
     p.add_argument("--in-crop-width", type=int, default=0, help="width of the window (see --in-crop-x); 0 (default) = no crop")
     p.add_argument("--in-crop-height", type=int, default=0, help="height of the window (see --in-crop-x); 0 (default) = no crop")
+    p.add_argument("--deinterlace", type=str, default="off", choices=["off", "linear", "edge"],
+                   help="take every input frame as two fields woven into its even and odd rows and deinterlace it on the GPU, in front of the crop "
+                        "and the resize (include/crtfx_deint.h): the rows between a field's rows are the mean of the rows above and below (linear) "
+                        "or of two of their pixels along the best of five directions per pixel (edge); off (default) = a progressive input")
+    p.add_argument("--field-order", type=str, default="tff", choices=["tff", "bff"],
+                   help="which field of an interlaced input comes first: the even rows (tff, default) or the odd rows (bff); needs --deinterlace")
+    p.add_argument("--deinterlace-fields", type=str, default="first", choices=["first", "both"],
+                   help="write one frame per input frame, made for its first field (first, default), or one per field in field order (both: twice "
+                        "the frames; pass the field rate as --fps); needs --deinterlace")
     return p
+
+
+def deinterlace_from_args(a):
+    """(method, order, fields) of --deinterlace / --field-order / --deinterlace-fields, or None for a progressive input."""
+    method, order, fields = getattr(a, "deinterlace", "off"), getattr(a, "field_order", "tff"), getattr(a, "deinterlace_fields", "first")
+    if method == "off":
+        if order != "tff" or fields != "first":
+            raise SystemExit(f"--field-order {order} / --deinterlace-fields {fields} without --deinterlace linear | edge: there is nothing to deinterlace")
+        return None
+    return method, order, fields
 
 
 def settings_from_args(a):
@@ -338,6 +367,7 @@ def main_sharded(a, rank: int, world: int) -> int:
         raise SystemExit("--deliver-width / --deliver-height are not supported by the sharded CLI (one process per GPU writes rgb24 at render size); "
                          "run one process, or scale behind it")
     for flag, on in (("--in-crop-x / --in-crop-y / --in-crop-width / --in-crop-height", any(getattr(a, "in_crop_" + k, 0) for k in ("x", "y", "width", "height"))),
+                     ("--deinterlace / --field-order / --deinterlace-fields", deinterlace_from_args(a) is not None),
                      ("--deliver-fit", getattr(a, "deliver_fit", "stretch") != "stretch"),
                      ("--deliver-pad-color", str(getattr(a, "deliver_pad_color", "0,0,0")) != "0,0,0")):
         if on:
@@ -495,6 +525,7 @@ def check_flags(a):
     if getattr(a, "dither", "none") != "none" and (not half or deep_out):
         raise SystemExit(f"--dither {a.dither} with --chain-pix {getattr(a, 'chain_pix', 'auto')} and --out-pix-fmt {a.out_pix_fmt}: only half frames "
                          "narrowed to an 8-bit output are dithered; pass --chain-pix half and an 8-bit or rgb24 --out-pix-fmt")
+    deint = deinterlace_from_args(a)
     deliver = deliver_size_from_args(a)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("CRTFX_FORCE_DIST") == "1":
         if a.gui or not a.input or a.width <= 0 or a.height <= 0:
@@ -506,6 +537,8 @@ def check_flags(a):
         raise SystemExit("the GUI is not part of this path; pass --input (raw rgb24 / yuv420p / nv12 / yuv422p / yuyv422 / uyvy422 / yuv420p10le / p010le / yuv444p10le / gbrp10le / x2rgb10le file or '-')")
     if a.width <= 0 or a.height <= 0:
         raise SystemExit("raw input needs --width and --height")
+    if deint is not None and a.height < 2:
+        raise SystemExit(f"--deinterlace {deint[0]} with --height {a.height}: a frame of one row has no two fields")
     if not half and deep != deep_out:
         raise SystemExit(f"--in-pix-fmt {a.in_pix_fmt} with --out-pix-fmt {a.out_pix_fmt}: a 10-bit format on one end only; the chain between them "
                          "runs on half pixels or on uint8 ones — pass yuv420p10le / p010le (or yuv444p10le / gbrp10le / x2rgb10le) on both ends "
@@ -517,8 +550,9 @@ def check_flags(a):
     return deliver, deep or half, None
 
 
-def open_output(a, fin, out_path: str, B: int, in_bytes: int, out_bytes: int):
-    """Open the output.  -> it, is each end a regular file (positional I/O; else sequential)?, pipe buffer sizes, [(offset, bytes)] per batch | None."""
+def open_output(a, fin, out_path: str, B: int, in_bytes: int, out_bytes: int, ratio: int = 1):
+    """Open the output.  -> it, is each end a regular file (positional I/O; else sequential)?, pipe buffer sizes, [(offset, bytes)] per batch | None.
+    `B` counts delivery frames per batch, `ratio` of them per input frame (2 under --deinterlace-fields both; B is then even)."""
     from .staging import _grow_pipe, _seekable
     in_pos = _seekable(fin) and a.input != "-"
     # opened with read access too (a MAP_SHARED, PROT_WRITE mapping needs O_RDWR).  --io mapped | auto only: an existing regular output behind a regular
@@ -534,7 +568,7 @@ def open_output(a, fin, out_path: str, B: int, in_bytes: int, out_bytes: int):
     # a regular input file fixes the output file's size: it can be sized, mapped and registered up front (a stream's goes through the pinned slots)
     out_plan = None
     if in_pos and out_pos:
-        n_total = os.fstat(fin.fileno()).st_size // in_bytes
+        n_total = os.fstat(fin.fileno()).st_size // in_bytes * ratio
         out_plan = [(k * B * out_bytes, min(B, n_total - k * B) * out_bytes) for k in range((n_total + B - 1) // B)] or None
         if presize and out_pos:
             os.ftruncate(fout.fileno(), n_total * out_bytes)
@@ -543,12 +577,16 @@ def open_output(a, fin, out_path: str, B: int, in_bytes: int, out_bytes: int):
 
 def feed(pipe, source, end, reader, writer, NS: int, fout, timed: bool):
     """The feed loop: every batch of the reader is uploaded, run through [source] -> chain -> [delivery end] and downloaded to the writer, on three
-    streams chained by events.  `fout`: the output if a regular file.  Returns the frames enqueued, the timing events, the seconds per leg."""
+    streams chained by events.  `fout`: the output if a regular file.  Returns the frames enqueued, the timing events, the seconds per leg.
+    The reader's batches count input frames; a source that deinterlaces to both fields (source.ratio = 2) makes two chain frames of each, and
+    everything behind it — frame indices, the writer, the return value — counts those."""
     import torch
-    dev, B, in_bytes, out_bytes = pipe.device, reader.shape[0], reader.frame_bytes, end.frame_bytes
+    dev, Bs, in_bytes, out_bytes = pipe.device, reader.shape[0], reader.frame_bytes, end.frame_bytes
+    ratio = 1 if source is None else source.ratio
+    B = Bs * ratio
     reader.start()
     dev_in, dev_out = ([torch.empty((B, pipe.h, pipe.w, 3), dtype=pipe.dtype, device=dev) for _ in range(NS)] for _ in range(2))
-    dev_recv = dev_in if source is None else source.slots(B, NS, pinned=False).dev         # what is uploaded
+    dev_recv = dev_in if source is None else source.slots(Bs, NS, pinned=False).dev        # what is uploaded
     end.slots(dev_out)                                              # what the egress plan reads, what is downloaded
     compute, s_up, s_down = torch.cuda.current_stream(dev), torch.cuda.Stream(dev), torch.cuda.Stream(dev)
     kernels_done, down_done = [None] * NS, [None] * NS      # per device slot: its batch's kernels (dev_in free again) / download (dev_out free again)
@@ -567,6 +605,7 @@ def feed(pipe, source, end, reader, writer, NS: int, fout, timed: bool):
             if item is None:
                 break
             i, n, got = item                                            # a trailing partial frame is dropped, as ffmpeg's rawvideo demuxer does
+            m = n * ratio                                               # the frames the chain runs and the writer gets
             tt = time.perf_counter()
             if n:
                 d = k % NS
@@ -583,9 +622,9 @@ def feed(pipe, source, end, reader, writer, NS: int, fout, timed: bool):
                 k0 = mark(compute) if timed else None
                 # on the compute stream and counted with the kernels (k0 ... kd): dev_in[d]'s last reader (batch k - NS) ran on this stream
                 if source is not None:
-                    source.convert(d, n, dev_in[d][:n])
-                _, state = pipe.run(dev_in[d][:n], first_index=index, state=state, out=dev_out[d][:n])
-                send = end.run(d, n)
+                    source.convert(d, n, dev_in[d][:m])
+                _, state = pipe.run(dev_in[d][:m], first_index=index, state=state, out=dev_out[d][:m])
+                send = end.run(d, m)
                 kd = mark(compute)
                 kernels_done[d] = kd
                 # download k on the third stream into a free pinned slot; the writer thread takes it from there
@@ -596,13 +635,13 @@ def feed(pipe, source, end, reader, writer, NS: int, fout, timed: bool):
                 tt = time.perf_counter()
                 s_down.wait_event(kd)
                 d0 = mark(s_down) if timed else None
-                writer.download(j, n, send, s_down)               # into the pinned slot, or straight into the registered output mapping
+                writer.download(j, m, send, s_down)               # into the pinned slot, or straight into the registered output mapping
                 dn = mark(s_down)
                 down_done[d] = dn
                 if timed:
-                    marks.append((u0, up, k0, kd, d0, dn, n))
-                writer.put(j, n, dn, out_off if fout is not None else None)
-                out_off += n * out_bytes
+                    marks.append((u0, up, k0, kd, d0, dn, n, m))
+                writer.put(j, m, dn, out_off if fout is not None else None)
+                out_off += m * out_bytes
             # a pinned input slot goes back once its upload has completed: the PREVIOUS batch's (long done), never the one just enqueued
             t_enq += time.perf_counter() - tt
             tt = time.perf_counter()
@@ -615,9 +654,9 @@ def feed(pipe, source, end, reader, writer, NS: int, fout, timed: bool):
                 pend = (up, i)
             else:
                 reader.release(i)
-            index += n
+            index += m
             k += 1
-            if got < B * in_bytes:
+            if got < Bs * in_bytes:
                 break
         if pend is not None:
             pend[0].synchronize()
@@ -654,7 +693,7 @@ def staging_report(index: int, marks, waits, times, reader, writer, pipes) -> No
         up_ms, k_ms, dn_ms = (sum(m[i].elapsed_time(m[i + 1]) for m in mk) / len(mk) for i in (0, 2, 4))
         span = mk[0][0].elapsed_time(mk[-1][5]) / len(mk)
         nf = sum(m[6] for m in mk) / len(mk)
-        nb, nb_out = nf * in_bytes, nf * out_bytes
+        nb, nb_out = nf * in_bytes, sum(m[7] for m in mk) / len(mk) * out_bytes       # frames read, frames written (two per frame read under --deinterlace-fields both)
         print(f"staging (GPU side, per batch of {nf:.0f} frames): upload {up_ms:.2f} ms = {nb / up_ms / 1e6:.1f} GB/s, kernels {k_ms:.2f} ms, "
               f"download {dn_ms:.2f} ms = {nb_out / dn_ms / 1e6:.1f} GB/s; one batch every {span:.2f} ms = {nf / span * 1e3:.0f} frames/s", file=sys.stderr)
     t_get, t_enq, t_slot, t_rel = waits
@@ -697,16 +736,21 @@ def main(argv=None) -> int:
     fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb", buffering=0)
     out_path = a.output if a.output else (a.input + "_crt.rgb" if a.input != "-" else "-")
     B, NS = max(1, int(a.batch)), 3
+    deint = deinterlace_from_args(a)                               # an interlaced input: every format then has a source end, rgb24 too
+    ratio = 2 if deint is not None and deint[2] == "both" else 1    # delivery frames per input frame
+    if ratio == 2:
+        B = max(2, B - B % 2)                                      # the chain's batch: both fields of B // 2 input frames
+    Bs = B // ratio                                                # input frames per batch
     end = DeliveryEnd(dev, (h, w), pix, a.out_pix_fmt, a.out_matrix, a.out_range, a.out_chroma, deliver, a.deliver_filter, a.deliver_fit, pad_color_from_args(a),
                       narrow=narrow)
     crop = in_crop_from_args(a)                                    # a window of the input: an rgb24 input then has a source end too
-    source = (SourceEnd(dev, (h, w), a.in_pix_fmt, a.in_matrix, a.in_range, a.in_chroma, (h, w), a.in_filter, crop, pix, widen=widen)
-              if a.in_pix_fmt != "rgb24" or crop is not None or widen else None)    # half chain: an rgb24 input goes through a Widen
+    source = (SourceEnd(dev, (h, w), a.in_pix_fmt, a.in_matrix, a.in_range, a.in_chroma, (h, w), a.in_filter, crop, pix, widen=widen, deinterlace=deint)
+              if a.in_pix_fmt != "rgb24" or crop is not None or widen or deint is not None else None)    # half chain: an rgb24 input goes through a Widen
     in_bytes = h * w * 3 if source is None else source.frame_bytes
     t0 = time.perf_counter()
-    fout, in_pos, out_pos, pipes, out_plan = open_output(a, fin, out_path, B, in_bytes, end.frame_bytes)
-    jobs = ((k * B * in_bytes if in_pos else None, B) for k in itertools.count())     # whole batches until the stream ends (the reader stops at a short read)
-    reader = _Reader(fin, in_pos, jobs, (B, h, w, 3) if source is None else (B,) + source.frame_shape, in_bytes, slots=NS, io=a.io, autostart=False)
+    fout, in_pos, out_pos, pipes, out_plan = open_output(a, fin, out_path, B, in_bytes, end.frame_bytes, ratio)
+    jobs = ((k * Bs * in_bytes if in_pos else None, Bs) for k in itertools.count())     # whole batches until the stream ends (the reader stops at a short read)
+    reader = _Reader(fin, in_pos, jobs, (B, h, w, 3) if source is None else (Bs,) + source.frame_shape, in_bytes, slots=NS, io=a.io, autostart=False)
     writer = _Writer(fout, out_pos, end.shape(B), end.frame_bytes, slots=NS, plan=out_plan, io=a.io)
     t_pipe = time.perf_counter()                                    # the pipeline proper: first read issued ... last batch written (the --staging-report line)
     t_slots = t_pipe - t_start - t_imports - t_engine

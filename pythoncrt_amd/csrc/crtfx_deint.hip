@@ -1,0 +1,411 @@
+// crtfx_deint.hip — the deinterlace stage (include/crtfx_deint.h): two fields woven into one h x w x 3 frame become one or two progressive
+// frames.  A vec and a general kernel per (method, sample type, field mode), the host glue, the C entry points.
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
+#include <type_traits>
+
+#include "crtfx_deint.h"
+#include "crtfx_stage_host.h"
+
+namespace crtfx_deint_impl {
+
+struct linear { static constexpr const char* name = "linear"; };
+struct edge { static constexpr const char* name = "edge"; };
+struct first { static constexpr const char* name = "first"; };
+struct both { static constexpr const char* name = "both"; };
+struct vec { static constexpr const char* name = "vec"; };
+struct general { static constexpr const char* name = "general"; };
+
+// q = rint_to_even(min(max(4 f, 0), 1020)), NaN -> 0: crtfx_resize16's quantiser (crtfx_resize16.hip), word for word
+__device__ __forceinline__ int quantise(uint32_t bits16) {
+    float t = 4.0f * (float)__builtin_bit_cast(_Float16, (unsigned short)bits16);
+    t = t > 0.0f ? t : 0.0f;
+    t = t < 1020.0f ? t : 1020.0f;
+    return (int)rintf(t);
+}
+
+// the sample types: the code a sample's bits stand for in the arithmetic, and the bits of a result
+struct u8 {
+    static constexpr const char* name = "u8";
+    typedef uint8_t T;
+    static __device__ __forceinline__ int code(uint32_t bits) { return (int)bits; }
+    static __device__ __forceinline__ uint32_t bits(int q) { return (uint32_t)q; }
+};
+struct f16 {
+    static constexpr const char* name = "f16";
+    typedef uint16_t T;
+    static __device__ __forceinline__ int code(uint32_t bits) { return quantise(bits); }
+    // q / 4 on the 0..255 scale: exact, every quarter code is a half
+    static __device__ __forceinline__ uint32_t bits(int q) { return (uint32_t)__builtin_bit_cast(unsigned short, (_Float16)((float)q * 0.25f)); }
+};
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef u32x4 u32x4_dword_aligned __attribute__((aligned(4)));          // a 16-byte access at a dword-aligned address
+typedef u32x2 u32x2_dword_aligned __attribute__((aligned(4)));          // an 8-byte one
+
+// Launch constants.
+struct Args {
+    const uint8_t* src;
+    uint8_t* dst;
+    size_t src_stride, dst_stride;      // bytes; the destination's is per OUTPUT frame
+    uint32_t h, w;
+    uint32_t blocks_row;                // vec: 8-pixel blocks per row (w / 8)
+    uint32_t lanes;                     // vec: lanes per source frame (h * blocks_row)
+    uint32_t first;                     // the field of output frame 0: 0 under TFF, 1 under BFF
+};
+
+constexpr int BLOCK = 256;
+constexpr int REACH = 3;                // columns the direction search reaches on either side of a pixel
+
+// The direction search of crtfx_deint.h for NP neighbouring pixels.  A and B are the kept rows above and below as codes, pixel i of the NP at
+// window index i + REACH; d[i] is the direction taken.  Branch-free: S(2j) counts only behind a successful S(j).
+template <int NP>
+__device__ __forceinline__ void edge_search(const int (&A)[NP + 2 * REACH][3], const int (&B)[NP + 2 * REACH][3], int (&d)[NP]) {
+    int s[NP];
+    bool step[NP] = {};
+#pragma unroll
+    for (int jj = 0; jj < 5; ++jj) {
+        constexpr int order[5] = {0, -1, -2, 1, 2};
+        const int j = order[jj];
+        int D[NP + 2];                  // D[c]: the three channels' |a - b| of the pixel pair centred at window index c + REACH - 1
+#pragma unroll
+        for (int c = 0; c < NP + 2; ++c) {
+            int v = 0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int t = A[c + REACH - 1 + j][k] - B[c + REACH - 1 - j][k];
+                v += t < 0 ? -t : t;
+            }
+            D[c] = v;
+        }
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int S = D[i] + D[i + 1] + D[i + 2];
+            if (j == 0) { s[i] = S - 1; d[i] = 0; continue; }
+            const bool take = ((j == -1 || j == 1) || step[i]) && S < s[i];
+            s[i] = take ? S : s[i];
+            d[i] = take ? j : d[i];
+            if (j == -1 || j == 1) step[i] = take;
+        }
+    }
+}
+
+// n dwords at a dword-aligned address, as 16-, 8- and 4-byte pieces
+template <int N>
+__device__ __forceinline__ void load_dwords(const uint8_t* __restrict__ p, uint32_t* out) {
+    static_assert(N % 2 == 0 || N == 3, "pieces");
+    if constexpr (N == 3) {
+        const u32x2 q = *reinterpret_cast<const u32x2_dword_aligned*>(p);
+        out[0] = q.x; out[1] = q.y; out[2] = *reinterpret_cast<const uint32_t*>(p + 8);
+    } else {
+#pragma unroll
+        for (int i = 0; i + 4 <= N; i += 4) {
+            const u32x4 q = *reinterpret_cast<const u32x4_dword_aligned*>(p + 4 * i);
+            out[i] = q.x; out[i + 1] = q.y; out[i + 2] = q.z; out[i + 3] = q.w;
+        }
+        if constexpr (N % 4 == 2) {
+            const u32x2 q = *reinterpret_cast<const u32x2_dword_aligned*>(p + 4 * (N - 2));
+            out[N - 2] = q.x; out[N - 1] = q.y;
+        }
+    }
+}
+
+template <int N>
+__device__ __forceinline__ void store_dwords(uint8_t* __restrict__ p, const uint32_t* in) {
+    static_assert(N % 2 == 0, "pieces");
+#pragma unroll
+    for (int i = 0; i + 4 <= N; i += 4) {
+        const u32x4 q = {in[i], in[i + 1], in[i + 2], in[i + 3]};
+        *reinterpret_cast<u32x4_dword_aligned*>(p + 4 * i) = q;
+    }
+    if constexpr (N % 4 == 2) {
+        const u32x2 q = {in[N - 2], in[N - 1]};
+        *reinterpret_cast<u32x2_dword_aligned*>(p + 4 * (N - 2)) = q;
+    }
+}
+
+// vec: one lane per 1 row x 8 pixels of the SOURCE frame: that block of every output frame is this lane's
+template <class M, class P, class F>
+__device__ __forceinline__ void deint_vec(const Args& a) {
+    constexpr int SZ = sizeof(typename P::T), SPD = 4 / SZ;            // bytes per sample, samples per dword
+    constexpr int CD = 24 / SPD, HD = 12 / SPD;                         // dwords of a block's 24 samples, and of the 4 pixels beside it
+    constexpr uint32_t MASK = SZ == 1 ? 0xffu : 0xffffu;
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= a.lanes) return;
+    const uint32_t y = i / a.blocks_row, bx = i - y * a.blocks_row;
+    const size_t row = (size_t)a.w * 3u * SZ, col = (size_t)bx * 24u * SZ;
+    const uint8_t* __restrict__ s = a.src + (size_t)blockIdx.z * a.src_stride;
+    const uint32_t kept = ((y & 1u) == a.first) ? 1u : 0u;              // row y is kept in output frame 0 (the first field's) and made in frame 1, or the reverse
+    uint8_t* __restrict__ dk;                                           // where row y is kept
+    uint8_t* __restrict__ dm;                                           // where row y is made
+    if constexpr (std::is_same<F, both>::value) {
+        dk = a.dst + ((size_t)blockIdx.z * 2u + (1u - kept)) * a.dst_stride + (size_t)y * row + col;
+        dm = a.dst + ((size_t)blockIdx.z * 2u + kept) * a.dst_stride + (size_t)y * row + col;
+    } else {
+        dk = dm = a.dst + (size_t)blockIdx.z * a.dst_stride + (size_t)y * row + col;
+    }
+    if (std::is_same<F, both>::value || kept) {                        // kept: the source's bits
+        uint32_t c[CD];
+        load_dwords<CD>(s + (size_t)y * row + col, c);
+        store_dwords<CD>(dk, c);
+    }
+    if (!std::is_same<F, both>::value && kept) return;
+    const bool two = y > 0u && y + 1u < a.h;                            // h >= 2: at least one neighbour row is in the frame
+    const uint8_t* __restrict__ ra = s + (size_t)(y > 0u ? y - 1u : y + 1u) * row + col;
+    const uint8_t* __restrict__ rb = s + (size_t)(y + 1u < a.h ? y + 1u : y - 1u) * row + col;
+    uint32_t out[CD];
+    if (!std::is_same<M, edge>::value || !two) {                        // LINEAR, and a row with one neighbour (a == b)
+        uint32_t ca[CD], cb[CD];
+        load_dwords<CD>(ra, ca);
+        if (two) load_dwords<CD>(rb, cb);
+#pragma unroll
+        for (int k = 0; k < CD; ++k) {
+            if (!two) cb[k] = ca[k];
+            if constexpr (SZ == 1) {
+                out[k] = (ca[k] | cb[k]) - (((ca[k] ^ cb[k]) >> 1) & 0x7f7f7f7fu);     // (a + b + 1) >> 1 in each byte
+            } else {
+                const int lo = (P::code(ca[k] & MASK) + P::code(cb[k] & MASK) + 1) >> 1, hi = (P::code(ca[k] >> 16) + P::code(cb[k] >> 16) + 1) >> 1;
+                out[k] = P::bits(lo) | P::bits(hi) << 16;
+            }
+        }
+    } else {
+        // the 16 pixels x0 - 4 .. x0 + 11 of both rows: the block and the four pixels on either side, which are blocks of the same row.  A
+        // block at a row's end has no such side; its slots stay zero and only pixels that take d = 0 would have looked at them.
+        uint32_t wa[CD + 2 * HD] = {}, wb[CD + 2 * HD] = {};
+        load_dwords<CD>(ra, wa + HD);
+        load_dwords<CD>(rb, wb + HD);
+        if (bx > 0u) { load_dwords<HD>(ra - 4 * HD, wa); load_dwords<HD>(rb - 4 * HD, wb); }
+        if (bx + 1u < a.blocks_row) { load_dwords<HD>(ra + 4 * CD, wa + HD + CD); load_dwords<HD>(rb + 4 * CD, wb + HD + CD); }
+        int A[8 + 2 * REACH][3], B[8 + 2 * REACH][3];                   // window index i <-> pixel x0 - 3 + i: sample 3 (i + 1) + k of the 48 loaded
+#pragma unroll
+        for (int p = 0; p < 8 + 2 * REACH; ++p)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int sidx = 3 * (p + 1) + k;
+                A[p][k] = P::code((wa[sidx / SPD] >> (8 * SZ * (sidx % SPD))) & MASK);
+                B[p][k] = P::code((wb[sidx / SPD] >> (8 * SZ * (sidx % SPD))) & MASK);
+            }
+        int d[8];
+        edge_search<8>(A, B, d);
+        const uint32_t x0 = bx * 8u;
+#pragma unroll
+        for (int k = 0; k < CD; ++k) out[k] = 0u;
+#pragma unroll
+        for (int p = 0; p < 8; ++p) {
+            const int dd = (x0 + p >= (uint32_t)REACH && x0 + p + REACH < a.w) ? d[p] : 0;      // x < 3 or x > w - 4: d = 0
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                int va = A[p + REACH][k], vb = B[p + REACH][k];
+#pragma unroll
+                for (int j = -2; j <= 2; ++j) {
+                    if (j == 0) continue;
+                    va = dd == j ? A[p + REACH + j][k] : va;
+                    vb = dd == j ? B[p + REACH - j][k] : vb;
+                }
+                const int sidx = 3 * p + k;
+                out[sidx / SPD] |= P::bits((va + vb + 1) >> 1) << (8 * SZ * (sidx % SPD));
+            }
+        }
+    }
+    store_dwords<CD>(dm, out);
+}
+
+// general: one lane per pixel of the SOURCE frame: that pixel of every output frame is this lane's
+template <class M, class P, class F>
+__device__ __forceinline__ void deint_general(const Args& a) {
+    typedef typename P::T T;
+    const uint32_t x = blockIdx.x * BLOCK + threadIdx.x, y = blockIdx.y;
+    if (x >= a.w) return;
+    const size_t row = (size_t)a.w * 3u, o = (size_t)y * row + (size_t)x * 3u;
+    const T* __restrict__ s = reinterpret_cast<const T*>(a.src + (size_t)blockIdx.z * a.src_stride);
+    const uint32_t kept = ((y & 1u) == a.first) ? 1u : 0u;
+    T* __restrict__ dk;
+    T* __restrict__ dm;
+    if constexpr (std::is_same<F, both>::value) {
+        dk = reinterpret_cast<T*>(a.dst + ((size_t)blockIdx.z * 2u + (1u - kept)) * a.dst_stride);
+        dm = reinterpret_cast<T*>(a.dst + ((size_t)blockIdx.z * 2u + kept) * a.dst_stride);
+    } else {
+        dk = dm = reinterpret_cast<T*>(a.dst + (size_t)blockIdx.z * a.dst_stride);
+    }
+    if (std::is_same<F, both>::value || kept) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) dk[o + k] = s[o + k];
+    }
+    if (!std::is_same<F, both>::value && kept) return;
+    const bool two = y > 0u && y + 1u < a.h;
+    const T* __restrict__ ra = s + (size_t)(y > 0u ? y - 1u : y + 1u) * row;
+    const T* __restrict__ rb = s + (size_t)(y + 1u < a.h ? y + 1u : y - 1u) * row;
+    int dd = 0;
+    if constexpr (std::is_same<M, edge>::value) {
+        if (two && x >= (uint32_t)REACH && x + REACH < a.w) {           // columns x - 3 .. x + 3 are in the row
+            int A[1 + 2 * REACH][3], B[1 + 2 * REACH][3], d[1];
+#pragma unroll
+            for (int p = 0; p < 1 + 2 * REACH; ++p)
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    A[p][k] = P::code(ra[(size_t)(x - REACH + p) * 3u + k]);
+                    B[p][k] = P::code(rb[(size_t)(x - REACH + p) * 3u + k]);
+                }
+            edge_search<1>(A, B, d);
+            dd = d[0];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k)                                         // |dd| <= 2 < REACH: inside the row
+        dm[o + k] = (T)P::bits((P::code(ra[(size_t)((int)x + dd) * 3u + k]) + P::code(rb[(size_t)((int)x - dd) * 3u + k]) + 1) >> 1);
+}
+
+template <class M, class P, class F, class Path>
+__global__ __launch_bounds__(BLOCK) void k_deint(Args a) {
+    if constexpr (std::is_same<Path, vec>::value) deint_vec<M, P, F>(a); else deint_general<M, P, F>(a);
+}
+
+}  // namespace crtfx_deint_impl
+
+using namespace crtfx_deint_impl;
+
+struct crtfx_deint {
+    int device = 0;
+    int h = 0, w = 0;
+    bool half = false, edge = false, bff = false, both = false;
+    size_t frame_bytes = 0;             // of one frame, source or output
+    bool force_general = false;
+    char plan[128] = "";
+    std::string err;
+};
+
+namespace {
+
+using crtfx_stage::DeviceGuard;
+using crtfx_stage::create_err;
+using crtfx_stage::fail;
+
+using H = crtfx_deint;
+
+// the vec kernels' conditions (crtfx_deint.h); n counts source frames
+bool vec_fits(const H* p, const void* src, size_t src_stride, const void* dst, size_t dst_stride, int n) {
+    if (p->force_general || (p->w & 7)) return false;
+    if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 3u) return false;
+    if (n > 1 && (src_stride & 3u)) return false;
+    return (size_t)n * (p->both ? 2 : 1) <= 1 || !(dst_stride & 3u);
+}
+
+void note_plan(H* p, bool fits, int frames) {
+    snprintf(p->plan, sizeof p->plan, "deint=k_deint<%s,%s,%s,%s>;frames=%d", p->edge ? edge::name : linear::name, p->half ? f16::name : u8::name,
+             p->both ? both::name : first::name, fits ? vec::name : general::name, frames);
+}
+
+template <class M, class P, class F>
+void launch_path(bool fits, dim3 grid, hipStream_t st, const Args& a) {
+    if (fits) hipLaunchKernelGGL((k_deint<M, P, F, vec>), grid, dim3(BLOCK), 0, st, a);
+    else hipLaunchKernelGGL((k_deint<M, P, F, general>), grid, dim3(BLOCK), 0, st, a);
+}
+
+template <class M, class P>
+void launch_fields(const H* p, bool fits, dim3 grid, hipStream_t st, const Args& a) {
+    if (p->both) launch_path<M, P, both>(fits, grid, st, a); else launch_path<M, P, first>(fits, grid, st, a);
+}
+
+template <class M>
+void launch_pix(const H* p, bool fits, dim3 grid, hipStream_t st, const Args& a) {
+    if (p->half) launch_fields<M, f16>(p, fits, grid, st, a); else launch_fields<M, u8>(p, fits, grid, st, a);
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* crtfx_deint_last_error(const crtfx_deint* p) { return p ? p->err.c_str() : create_err<H>().c_str(); }
+
+int crtfx_deint_create(int device, int h, int w, int pix_fmt, int method, int order, int fields, crtfx_deint** out_plan) {
+    create_err<H>().clear();
+    if (!out_plan) return fail<H>(nullptr, CRTFX_E_INVALID, "out_plan is null");
+    *out_plan = nullptr;
+    if (h < 2 || h > 32767) return fail<H>(nullptr, CRTFX_E_INVALID, "h = %d outside 2..32767 (a frame of two fields has two rows)", h);
+    if (w < 1 || w > 32767) return fail<H>(nullptr, CRTFX_E_INVALID, "w = %d outside 1..32767", w);
+    if (pix_fmt != CRTFX_PIX_U8 && pix_fmt != CRTFX_PIX_F16) return fail<H>(nullptr, CRTFX_E_INVALID, "unknown pix_fmt %d", pix_fmt);
+    if (method != CRTFX_DEINT_LINEAR && method != CRTFX_DEINT_EDGE) return fail<H>(nullptr, CRTFX_E_INVALID, "unknown method %d", method);
+    if (order != CRTFX_DEINT_TFF && order != CRTFX_DEINT_BFF) return fail<H>(nullptr, CRTFX_E_INVALID, "unknown order %d", order);
+    if (fields != CRTFX_DEINT_FIRST && fields != CRTFX_DEINT_BOTH) return fail<H>(nullptr, CRTFX_E_INVALID, "unknown fields %d", fields);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail<H>(nullptr, CRTFX_E_HIP, "no HIP device %d", device);
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return fail<H>(nullptr, CRTFX_E_HIP, "hipSetDevice(%d): %s", device, hipGetErrorString(guard.err));
+    H* p = new (std::nothrow) H();
+    if (!p) return fail<H>(nullptr, CRTFX_E_NOMEM, "out of host memory");
+    p->device = device; p->h = h; p->w = w;
+    p->half = pix_fmt == CRTFX_PIX_F16; p->edge = method == CRTFX_DEINT_EDGE; p->bff = order == CRTFX_DEINT_BFF; p->both = fields == CRTFX_DEINT_BOTH;
+    p->frame_bytes = (size_t)h * w * 3 * (p->half ? 2 : 1);
+    note_plan(p, vec_fits(p, nullptr, 0, nullptr, 0, 1), 0);
+    *out_plan = p;
+    return CRTFX_OK;
+}
+
+int crtfx_deint_frames_out(const crtfx_deint* p) { return !p ? 0 : p->both ? 2 : 1; }
+
+int crtfx_deint_destroy(crtfx_deint* p) {
+    if (!p) return CRTFX_OK;
+    DeviceGuard guard(p->device);
+    (void)hipDeviceSynchronize();
+    delete p;
+    return CRTFX_OK;
+}
+
+int crtfx_deint_set_option(crtfx_deint* p, int option, int value) {
+    if (!p) return CRTFX_E_INVALID;
+    if (option != CRTFX_DEINT_OPT_FORCE_GENERAL) return fail(p, CRTFX_E_INVALID, "unknown deint option %d", option);
+    if (value != 0 && value != 1) return fail(p, CRTFX_E_INVALID, "FORCE_GENERAL takes 0 or 1, got %d", value);
+    p->force_general = value != 0;
+    note_plan(p, vec_fits(p, nullptr, 0, nullptr, 0, 1), 0);
+    return CRTFX_OK;
+}
+
+int crtfx_deint_last_plan(crtfx_deint* p, char* buf, size_t n) {
+    if (!p || !buf || n == 0) return CRTFX_E_INVALID;
+    snprintf(buf, n, "%s", p->plan);
+    return CRTFX_OK;
+}
+
+int crtfx_deint_run(crtfx_deint* p, const void* src_base, size_t src_stride_bytes, void* dst_base, size_t dst_stride_bytes, int n, void* stream) {
+    if (!p) return CRTFX_E_INVALID;
+    if (n < 0) return fail(p, CRTFX_E_INVALID, "n = %d frames", n);
+    if (n == 0) { note_plan(p, vec_fits(p, src_base, src_stride_bytes, dst_base, dst_stride_bytes, 0), 0); return CRTFX_OK; }
+    if (!src_base || !dst_base) return fail(p, CRTFX_E_INVALID, "null frame pointer");
+    const size_t n_out = (size_t)n * (p->both ? 2 : 1);
+    const uintptr_t sb = reinterpret_cast<uintptr_t>(src_base), db = reinterpret_cast<uintptr_t>(dst_base);
+    if (p->half && (((sb | db) & 1u) || (n > 1 && (src_stride_bytes & 1u)) || (n_out > 1 && (dst_stride_bytes & 1u))))
+        return fail(p, CRTFX_E_INVALID, "half frames need even bases and strides");
+    if ((n > 1 && src_stride_bytes < p->frame_bytes) || (n_out > 1 && dst_stride_bytes < p->frame_bytes))
+        return fail(p, CRTFX_E_INVALID, "frame strides %zu / %zu bytes are smaller than a frame (%zu)", src_stride_bytes, dst_stride_bytes, p->frame_bytes);
+    const uintptr_t se = sb + (size_t)(n - 1) * src_stride_bytes + p->frame_bytes, de = db + (n_out - 1) * dst_stride_bytes + p->frame_bytes;
+    if (sb < de && db < se) return fail(p, CRTFX_E_INVALID, "source and destination overlap");
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) return fail(p, CRTFX_E_HIP, "hipGetDevice failed");
+    if (dev != p->device) return fail(p, CRTFX_E_INVALID, "current device %d is not the plan's device %d (call hipSetDevice first)", dev, p->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool fits = vec_fits(p, src_base, src_stride_bytes, dst_base, dst_stride_bytes, n);
+    Args a{};
+    a.src_stride = src_stride_bytes; a.dst_stride = dst_stride_bytes;
+    a.h = (uint32_t)p->h; a.w = (uint32_t)p->w;
+    a.blocks_row = a.w / 8u;
+    a.lanes = a.h * a.blocks_row;                                       // below 2^27
+    a.first = p->bff ? 1u : 0u;
+    const int group = 32768;                                            // grid.z: source frames per launch
+    for (int f = 0; f < n; f += group) {
+        const unsigned g = n - f < group ? n - f : group;
+        a.src = static_cast<const uint8_t*>(src_base) + (size_t)f * src_stride_bytes;
+        a.dst = static_cast<uint8_t*>(dst_base) + (size_t)f * (p->both ? 2 : 1) * dst_stride_bytes;
+        const dim3 grid = fits ? dim3((a.lanes + BLOCK - 1) / BLOCK, 1, g) : dim3((a.w + BLOCK - 1) / BLOCK, p->h, g);
+        if (p->edge) launch_pix<edge>(p, fits, grid, st, a); else launch_pix<linear>(p, fits, grid, st, a);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(p, CRTFX_E_HIP, "deint launch: %s", hipGetErrorString(e));
+    }
+    note_plan(p, fits, n);
+    return CRTFX_OK;
+}
+
+}  // extern "C"

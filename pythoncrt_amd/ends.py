@@ -3,6 +3,7 @@
 from . import formats
 from ._stage import resize_plan
 from .canvas import Canvas, fit_crop, fit_pad
+from .deint import Deinterlace
 from .depth import Narrow, Widen
 
 
@@ -34,13 +35,21 @@ class SourceEnd(StagingSlots):
     window `crop` = (y, x, ch, cw) of the source frame], [resize of what is left to the render size] (ref:1039-1041).  The RGB side of the
     source plan, the window and the resize are frames of `dtype`.  With `widen` those are uint8 frames in front of a half chain: a Widen at
     the render size (include/crtfx_depth.h) is then the last stage and writes the chain's half input — for an rgb24 frame at render size
-    the only one."""
+    the only one.  `deinterlace` = (method, order, fields) puts a Deinterlace (include/crtfx_deint.h) directly behind the source plan, at
+    src_hw and on `dtype`, in front of the Canvas and the resize: a crop at an odd y, or any resize, would mix the fields.  `ratio` is the
+    frames it writes per source frame (1 without it): the staged slots hold SOURCE frames and convert(d, n, dst) writes n * ratio frames."""
 
-    def __init__(self, device, render_hw, in_pix_fmt, in_matrix, in_range, in_chroma, src_hw, in_filter, crop=None, dtype=None, widen=False):
+    def __init__(self, device, render_hw, in_pix_fmt, in_matrix, in_range, in_chroma, src_hw, in_filter, crop=None, dtype=None, widen=False,
+                 deinterlace=None):
         import torch
         self.device, self.src_hw = device, tuple(src_hw)
         self.dtype = torch.uint8 if dtype is None or widen else dtype      # widen: `dtype` is the chain's, the stages in front of it run on uint8
         self.plan = formats.source_plan(device, self.src_hw, in_pix_fmt, in_matrix, in_range, in_chroma)
+        self.deint, self.ratio = None, 1
+        if deinterlace is not None:
+            method, order, fields = deinterlace
+            self.deint = Deinterlace(device, self.src_hw, method=method, order=order, fields=fields, dtype=self.dtype)
+            self.ratio = 2 if fields == "both" else 1
         self.canvas, cut = None, self.src_hw
         if crop is not None:
             cut = (int(crop[2]), int(crop[3]))
@@ -50,20 +59,25 @@ class SourceEnd(StagingSlots):
         self.frame_bytes = formats.frame_bytes(*self.src_hw, in_pix_fmt) if self.plan is None else self.plan.frame_bytes
         self.frame_shape = self.src_hw + (3,) if self.plan is None else (self.frame_bytes,)
         # the stages present, each with the size of the RGB frames it writes; the last one writes the chain's input
-        self.stages = [(st, hw) for st, hw in ((self.plan, self.src_hw), (self.canvas, cut), (self.resize, tuple(render_hw)),
-                                                    (self.widen, tuple(render_hw))) if st is not None]
+        self.stages = [(st, hw) for st, hw in ((self.plan, self.src_hw), (self.deint, self.src_hw), (self.canvas, cut),
+                                                    (self.resize, tuple(render_hw)), (self.widen, tuple(render_hw))) if st is not None]
 
     def slots(self, B: int, NS: int, pinned: bool = True):
         import torch
         shape = (B,) + self.frame_shape
-        # a stage that is not the last one writes RGB slots of its own: a missing stage costs no buffer
-        self.mid = [[torch.empty((B,) + hw + (3,), dtype=self.dtype, device=self.device) for _ in range(NS)] for _, hw in self.stages[:-1]]
+        # a stage that is not the last one writes RGB slots of its own: a missing stage costs no buffer.  B counts source frames: the
+        # Deinterlace and every stage behind it write B * ratio frames
+        behind = [any(st is self.deint for st, _ in self.stages[:i + 1]) for i in range(len(self.stages))]
+        self.mid = [[torch.empty((B * (self.ratio if behind[i] else 1),) + hw + (3,), dtype=self.dtype, device=self.device) for _ in range(NS)]
+                    for i, (_, hw) in enumerate(self.stages[:-1])]
         return self.adopt([torch.empty(shape, dtype=torch.uint8, device=self.device) for _ in range(NS)],
                           [torch.empty(shape, dtype=torch.uint8).pin_memory() for _ in range(NS)] if pinned else None)
 
     def convert(self, d: int, n: int, dst):
         x = self.dev[d][:n]
         for i, (stage, _) in enumerate(self.stages):
+            if stage is self.deint:
+                n *= self.ratio
             x = stage.run(x, out=dst if i == len(self.stages) - 1 else self.mid[i][d][:n])
 
 

@@ -149,7 +149,8 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                    in_chroma: str = "replicate", out_chroma: str = "center", deliver_size: Optional[Tuple[int, int]] = None,
                    in_filter: str = "bilinear", deliver_filter: str = "bilinear", in_crop: Optional[Tuple[int, int, int, int]] = None,
                    deliver_fit: str = "stretch", deliver_pad_color: Tuple[int, int, int] = (0, 0, 0), chain_pix: str = "auto",
-                   dither: str = "none", **io_keywords) -> int:
+                   dither: str = "none", deinterlace: str = "off", field_order: str = "tff", deinterlace_fields: str = "first",
+                   **io_keywords) -> int:
     """Render every frame of `frame_iter` (H x W x 3 uint8 RGB arrays) and hand the finished uint8 frames to `write_frame` in order.
     Effect keywords: the names, meaning and defaults of process_video / the CLI (ref:864-911, :1155-1206); the caller applies the clamps of
     ref:1225-1266 as the reference's `main` does (`pythoncrt_amd.cli.settings_from_args` restates them).  Returns the number of frames written.
@@ -239,6 +240,21 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     bytes of "auto".  "auto" (default) is the path as it was, the one-end refusal included.  Refused with ValueError before a device is
     touched: an unknown `chain_pix` or `dither`; `dither` other than "none" where no Narrow would stand (`chain_pix="auto"`, or a 10-bit
     `out_pix_fmt`).
+    `deinterlace="linear"` / `"edge"` takes every source frame as two fields woven into its even and odd rows (480i / 576i / 1080i tapes,
+    consoles, camcorders, DVDs) and deinterlaces it on the device before anything else sees it: Deinterlace (include/crtfx_deint.h) stands
+    directly behind the source plan, at the source size, in front of `in_crop`'s Canvas and the resize, which would mix the fields.  The
+    rows of a field are kept; the rows between them are the rounded mean of the kept rows above and below ("linear") or of two pixels of
+    those rows along the best of five directions, chosen per pixel ("edge").  `field_order` "tff" (default) / "bff" says which field is the
+    first.  `deinterlace_fields="first"` (default) writes one frame per source frame, made for the first field; `"both"` writes two, one per
+    field in field order — a tube showed fields, not frames, and the persistence blend then decays field to field.  Under "both" a chain
+    batch of B frames is fed by B // 2 source frames, B = `batch` taken even and at least 2; frame indices, `written`, `progress_cb` and
+    the return value count frames WRITTEN (pass `total_frames` as such); the chain's clock stays `fps_out` as given: pass the FIELD rate
+    (59.94 for 29.97i).  Every source then goes through a source end, as under `in_crop` or `chain_pix="half"` — an rgb24 frame at render
+    size too — and an rgb24 frame of fewer than 2 rows raises ValueError.  "off" (default) is the path as it was: no Deinterlace is
+    created.  Known limit: the chroma rows of a 4:2:0 source are paired by its source plan as a progressive frame's are, in front of this
+    stage; 4:2:2, 4:4:4 and rgb24 sources have no such pairing.  Refused with ValueError before a device is touched: an unknown value of
+    the three keywords; `field_order` or `deinterlace_fields` off its default with "off" (there is nothing to deinterlace);
+    `resize_on="host"`; a source height below 2 where it is known (`in_size`, or the render size for a packed `in_pix_fmt`).
     If `frame_iter` or `write_frame` raises, the GPU work already queued is drained (device synchronize) before the exception leaves this
     function, so that the staging buffers are not freed under a running copy."""
     import os
@@ -277,6 +293,25 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         raise ValueError(f"chain_pix must be one of {', '.join(CHAIN_PIX)}, got {chain_pix!r} (dither={dither!r})")
     if dither not in DITHERS:
         raise ValueError(f"dither must be one of {', '.join(DITHERS)}, got {dither!r} (chain_pix={chain_pix!r})")
+    from .deint import FIELDS, METHODS, ORDERS
+    if deinterlace != "off" and deinterlace not in METHODS:
+        raise ValueError(f"deinterlace must be 'off' or one of {', '.join(METHODS)}, got {deinterlace!r}")
+    if field_order not in ORDERS:
+        raise ValueError(f"field_order must be one of {', '.join(ORDERS)}, got {field_order!r}")
+    if deinterlace_fields not in FIELDS:
+        raise ValueError(f"deinterlace_fields must be one of {', '.join(FIELDS)}, got {deinterlace_fields!r}")
+    if deinterlace == "off" and (field_order != "tff" or deinterlace_fields != "first"):
+        raise ValueError(f"field_order={field_order!r} / deinterlace_fields={deinterlace_fields!r} with deinterlace='off': there is nothing to "
+                         "deinterlace")
+    if deinterlace != "off":
+        if resize_on == "host":
+            raise ValueError(f"resize_on='host' cannot be combined with deinterlace={deinterlace!r}: the fields are separated on the device, in "
+                             "front of the resize")
+        src_h = int(in_size[0]) if in_size is not None else (int(out_h) if in_pix_fmt != "rgb24" else None)
+        if src_h is not None and src_h < 2:
+            raise ValueError(f"deinterlace={deinterlace!r}: a source frame of {src_h} row(s) has no two fields")
+    deint = None if deinterlace == "off" else (deinterlace, field_order, deinterlace_fields)
+    ratio = 2 if deint is not None and deinterlace_fields == "both" else 1      # frames written per source frame
     half = chain_pix == "half"
     deep, deep_out = formats.bits(in_pix_fmt) == 10, formats.bits(out_pix_fmt) == 10       # under "auto": both ends or neither
     if dither != "none" and (not half or deep_out):
@@ -306,6 +341,9 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         raise RuntimeError("no ROCm device visible; pythoncrt_amd has no CPU fallback")
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     h, w, B = int(out_h), int(out_w), max(1, int(batch))
+    if ratio == 2:
+        B = max(2, B - B % 2)                                                  # the chain's batch: both fields of B // 2 source frames
+    Bs = B // ratio                                                            # source frames per batch
     rs = RenderSettings(
         scanline_strength=float(scanline_strength), triad_strength=float(triad_strength), triad_gamma=float(triad_gamma),
         triad_preserve_luma=bool(triad_preserve_luma), triad_softness=float(triad_softness), aberration_px=int(aberration_px),
@@ -327,7 +365,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     total = max(1, int(total_frames)) if total_frames else None
 
     NS = 2
-    pin_in = [torch.empty((B, h, w, 3), dtype=torch.uint8).pin_memory() for _ in range(NS)] if in_pix_fmt == "rgb24" and not widen else None   # else: a SourceEnd's own
+    pin_in = [torch.empty((B, h, w, 3), dtype=torch.uint8).pin_memory() for _ in range(NS)] if in_pix_fmt == "rgb24" and not widen and deint is None else None   # else: a SourceEnd's own
     end = DeliveryEnd(dev, (h, w), pix, out_pix_fmt, out_matrix, out_range, out_chroma, deliver, deliver_filter, deliver_fit, pad_color,
                       narrow=narrow)
     pin_out = [torch.empty(end.shape(B), dtype=torch.uint8).pin_memory() for _ in range(NS)]    # what is downloaded and handed to the writer
@@ -356,7 +394,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                 torch.cuda.synchronize(dev)
                 sources.pop(next(iter(sources)))
             fmt, hw = (in_pix_fmt, yuv_hw) if key == YUV else ("rgb24", key)
-            src = SourceEnd(dev, (h, w), fmt, in_matrix, in_range, in_chroma, hw, in_filter, crop, pix, widen=widen).slots(B, NS)
+            src = SourceEnd(dev, (h, w), fmt, in_matrix, in_range, in_chroma, hw, in_filter, crop, pix, widen=widen, deinterlace=deint).slots(Bs, NS)
             assert key != YUV or src.frame_bytes == yuv_bytes
         sources[key] = src
         return src
@@ -373,6 +411,8 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
             return a, YUV
         if a.ndim != 3 or a.shape[2] != 3:
             raise ValueError(f"frames must be H x W x 3 RGB arrays, got {a.shape}")
+        if deint is not None and a.shape[0] < 2:
+            raise ValueError(f"deinterlace={deinterlace!r}: a frame of {a.shape[0]} x {a.shape[1]} has no two fields")
         if crop is not None:                                                    # every frame goes through a SourceEnd of ITS size
             if a.shape[0] < crop[0] + crop[2] or a.shape[1] < crop[1] + crop[3]:
                 raise ValueError(f"in_crop={crop}: the window leaves a frame of {a.shape[0]} x {a.shape[1]}")
@@ -382,7 +422,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                 return a, (int(a.shape[0]), int(a.shape[1]))
             from PIL import Image
             a = np.asarray(Image.fromarray(np.ascontiguousarray(a, dtype=np.uint8)).resize((w, h), getattr(Image, in_filter.upper())))
-        return a, ((h, w) if widen else None)                                   # a half chain: no direct upload, the frame goes through a Widen
+        return a, ((h, w) if widen or deint is not None else None)              # a half chain, a deinterlaced source: no direct upload, the frame goes through a source end
 
     def drain(p):
         nonlocal written
@@ -400,7 +440,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         while not done:
             d = k % NS
             n, key, src = 0, None, None
-            while n < B:
+            while n < Bs:
                 if carry is not None:
                     (a, akey), carry = carry, None
                 else:
@@ -430,28 +470,29 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                 src.up_done[d] = up
                 compute.wait_event(up)
                 # dev_in[d]: its last upload (two batches ago) was awaited by `compute` then, its last readers ran on `compute`
-                src.convert(d, n, dev_in[d][:n])                                     # on the compute stream; nothing for `direct`
+                m = n * ratio                        # the frames the chain runs and the writer gets: n source frames, `ratio` each
+                src.convert(d, n, dev_in[d][:m])                                     # on the compute stream; nothing for `direct`
                 if down_done[d] is not None:
                     compute.wait_event(down_done[d])
-                _, state = pipe.run(dev_in[d][:n], first_index=index, state=state, out=dev_out[d][:n])
-                send = end.run(d, n)                 # behind the chain on the compute stream; the slot's last download was awaited above
+                _, state = pipe.run(dev_in[d][:m], first_index=index, state=state, out=dev_out[d][:m])
+                send = end.run(d, m)                 # behind the chain on the compute stream; the slot's last download was awaited above
                 kd = torch.cuda.Event()
                 kd.record(compute)
                 direct.kernels_done[d] = src.kernels_done[d] = kd      # the kernels that last read dev_in[d] / wrote dev_out[d]
                 # pin_out[d] was drained one iteration ago (drain below runs before the next batch is enqueued into the same slot)
                 s_down.wait_event(kd)
                 with torch.cuda.stream(s_down):
-                    pin_out[d][:n].copy_(send, non_blocking=True)
+                    pin_out[d][:m].copy_(send, non_blocking=True)
                     dn = torch.cuda.Event()
                     dn.record(s_down)
                 down_done[d] = dn
-                index += n
+                index += m
             # the PREVIOUS batch's frames go to the writer while this batch is on the GPU
             if pending is not None:
                 drain(pending)
                 pending = None
             if n:
-                pending = (d, n, dn)
+                pending = (d, m, dn)
             k += 1
         if pending is not None:
             drain(pending)
