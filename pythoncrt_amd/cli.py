@@ -86,6 +86,21 @@ holds twice the input's frames.  A 480i uyvy422 capture sent as fields, no host 
              --deinterlace edge --field-order bff --deinterlace-fields both [effect flags] |
       ffmpeg -f rawvideo -pix_fmt rgb24 -s 720x480 -r 60000/1001 -i - out.mp4
 
+`--in-lut FILE` / `--deliver-lut FILE` apply a 3D colour LUT (a `.cube` file, tetrahedral interpolation; include/crtfx_lut3d.h) on the
+GPU directly in front of the chain and directly behind it, at `--width x --height` and on the chain's pixels — the `lut3d=` of a second
+ffmpeg process and its round trip through host memory.  `--in-lut` brings a log-encoded or HDR source to display-referred video before
+the tube sees it (behind the widening of `--chain-pix half`, so an 8-bit log source is transformed at half precision); `--deliver-lut`
+puts a look or display transform on the finished frames, in front of the delivery resize, the pad and the dither.  HDR10 to SDR with a
+PQ / BT.2020 -> BT.709 cube of your own:
+
+    ffmpeg -i hdr10.mkv -f rawvideo -pix_fmt p010le - |
+      python -m pythoncrt_amd.cli --input - --width 3840 --height 2160 --fps 24 --output - --in-pix-fmt p010le --out-pix-fmt yuv420p \
+             --chain-pix half --dither ordered --in-lut pq2020_to_709.cube [effect flags] |
+      ffmpeg -f rawvideo -pix_fmt yuv420p -s 3840x2160 -r 24 -i - out.mp4
+
+Cube sizes 2..65 and the domain 0..1 are taken; the cube's entries and the results are quarter codes (0..1020), so its precision is 10
+bits.  Without the flags nothing is created and the path is as it was.
+
 `--gui`, `--gpu`, `--nvenc-preset`, `--encoder`, `--decoder`, `--crf` and `--bitrate` are accepted for
 compatibility and ignored (encode/decode/UI are not part of this path).  `--text*` rasterise the overlay on
 the host with Pillow (ref:366-414) and alpha-blend it on the GPU before or after the effects.
@@ -216,7 +231,24 @@ def add_output_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--dither", type=str, default="none", choices=["none", "ordered"],
                    help="how --chain-pix half narrows its half frames to an 8-bit output: round to nearest (none, default) or 8 x 8 ordered (Bayer) "
                         "dither at the delivered frame's coordinates (ordered); needs --chain-pix half and an 8-bit or rgb24 --out-pix-fmt")
+    p.add_argument("--deliver-lut", type=str, default="", metavar="FILE",
+                   help="a .cube file (3D LUT, sizes 2..65, domain 0..1) applied to the finished frames on the GPU, directly behind the chain and in "
+                        "front of the delivery resize, the pad and the dither (include/crtfx_lut3d.h: tetrahedral, 10-bit entries); default: none")
     return p
+
+
+def luts_from_args(a):
+    """(in cube | None, delivery cube | None) of --in-lut / --deliver-lut, read once per parsed command line."""
+    if getattr(a, "_luts", None) is None:
+        from .cube import as_cube
+        cubes = []
+        for flag, path in (("--in-lut", getattr(a, "in_lut", "")), ("--deliver-lut", getattr(a, "deliver_lut", ""))):
+            try:
+                cubes.append(as_cube(path, flag) if path else None)
+            except ValueError as e:
+                raise SystemExit(f"{flag}: {e}") from None
+        a._luts = tuple(cubes)
+    return a._luts
 
 
 def deliver_size_from_args(a):
@@ -305,6 +337,10 @@ def add_input_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--deinterlace-fields", type=str, default="first", choices=["first", "both"],
                    help="write one frame per input frame, made for its first field (first, default), or one per field in field order (both: twice "
                         "the frames; pass the field rate as --fps); needs --deinterlace")
+    p.add_argument("--in-lut", type=str, default="", metavar="FILE",
+                   help="a .cube file (3D LUT, sizes 2..65, domain 0..1) applied to the source frames on the GPU at --width x --height, directly in "
+                        "front of the chain: behind the resize and, under --chain-pix half, behind the widening (include/crtfx_lut3d.h: "
+                        "tetrahedral, 10-bit entries) — log footage or HDR10 brought to display-referred video; default: none")
     return p
 
 
@@ -368,6 +404,7 @@ def main_sharded(a, rank: int, world: int) -> int:
                          "run one process, or scale behind it")
     for flag, on in (("--in-crop-x / --in-crop-y / --in-crop-width / --in-crop-height", any(getattr(a, "in_crop_" + k, 0) for k in ("x", "y", "width", "height"))),
                      ("--deinterlace / --field-order / --deinterlace-fields", deinterlace_from_args(a) is not None),
+                     ("--in-lut", bool(getattr(a, "in_lut", ""))), ("--deliver-lut", bool(getattr(a, "deliver_lut", ""))),
                      ("--deliver-fit", getattr(a, "deliver_fit", "stretch") != "stretch"),
                      ("--deliver-pad-color", str(getattr(a, "deliver_pad_color", "0,0,0")) != "0,0,0")):
         if on:
@@ -547,6 +584,7 @@ def check_flags(a):
     if deep and crop is not None and crop[2:] != (int(a.height), int(a.width)):
         raise SystemExit(f"--in-crop-width {crop[3]} --in-crop-height {crop[2]} differs from --width {a.width} x --height {a.height}: a 10-bit input "
                          "cannot be resized (IngestResize has no half path)")
+    luts_from_args(a)                                              # an unreadable or malformed cube
     return deliver, deep or half, None
 
 
@@ -741,11 +779,13 @@ def main(argv=None) -> int:
     if ratio == 2:
         B = max(2, B - B % 2)                                      # the chain's batch: both fields of B // 2 input frames
     Bs = B // ratio                                                # input frames per batch
+    in_cube, deliver_cube = luts_from_args(a)                      # --in-lut: every format then has a source end, rgb24 too
     end = DeliveryEnd(dev, (h, w), pix, a.out_pix_fmt, a.out_matrix, a.out_range, a.out_chroma, deliver, a.deliver_filter, a.deliver_fit, pad_color_from_args(a),
-                      narrow=narrow)
+                      narrow=narrow, **({} if deliver_cube is None else {"lut": deliver_cube}))
     crop = in_crop_from_args(a)                                    # a window of the input: an rgb24 input then has a source end too
-    source = (SourceEnd(dev, (h, w), a.in_pix_fmt, a.in_matrix, a.in_range, a.in_chroma, (h, w), a.in_filter, crop, pix, widen=widen, deinterlace=deint)
-              if a.in_pix_fmt != "rgb24" or crop is not None or widen or deint is not None else None)    # half chain: an rgb24 input goes through a Widen
+    source = (SourceEnd(dev, (h, w), a.in_pix_fmt, a.in_matrix, a.in_range, a.in_chroma, (h, w), a.in_filter, crop, pix, widen=widen, deinterlace=deint,
+                        **({} if in_cube is None else {"lut": in_cube}))
+              if a.in_pix_fmt != "rgb24" or crop is not None or widen or deint is not None or in_cube is not None else None)    # half chain: an rgb24 input goes through a Widen
     in_bytes = h * w * 3 if source is None else source.frame_bytes
     t0 = time.perf_counter()
     fout, in_pos, out_pos, pipes, out_plan = open_output(a, fin, out_path, B, in_bytes, end.frame_bytes, ratio)

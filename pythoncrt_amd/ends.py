@@ -5,6 +5,7 @@ from ._stage import resize_plan
 from .canvas import Canvas, fit_crop, fit_pad
 from .deint import Deinterlace
 from .depth import Narrow, Widen
+from .lut3d import Lut3D
 
 
 def depth_stages(in_pix_fmt: str, out_pix_fmt: str, chain_pix: str = "auto", dither: str = "none"):
@@ -37,10 +38,12 @@ class SourceEnd(StagingSlots):
     the render size (include/crtfx_depth.h) is then the last stage and writes the chain's half input — for an rgb24 frame at render size
     the only one.  `deinterlace` = (method, order, fields) puts a Deinterlace (include/crtfx_deint.h) directly behind the source plan, at
     src_hw and on `dtype`, in front of the Canvas and the resize: a crop at an odd y, or any resize, would mix the fields.  `ratio` is the
-    frames it writes per source frame (1 without it): the staged slots hold SOURCE frames and convert(d, n, dst) writes n * ratio frames."""
+    frames it writes per source frame (1 without it): the staged slots hold SOURCE frames and convert(d, n, dst) writes n * ratio frames.
+    `lut` is None or a Cube: a Lut3D (include/crtfx_lut3d.h) at the render size and on the CHAIN's pixel type is then the last stage,
+    behind the resize and behind the Widen, and writes the chain's input — for an rgb24 frame at render size the only one."""
 
     def __init__(self, device, render_hw, in_pix_fmt, in_matrix, in_range, in_chroma, src_hw, in_filter, crop=None, dtype=None, widen=False,
-                 deinterlace=None):
+                 deinterlace=None, lut=None):
         import torch
         self.device, self.src_hw = device, tuple(src_hw)
         self.dtype = torch.uint8 if dtype is None or widen else dtype      # widen: `dtype` is the chain's, the stages in front of it run on uint8
@@ -56,11 +59,14 @@ class SourceEnd(StagingSlots):
             self.canvas = Canvas(device, self.src_hw, cut, window=tuple(int(v) for v in crop), dtype=self.dtype)
         self.resize = resize_plan(device, cut, render_hw, in_filter, self.dtype) if cut != tuple(render_hw) else None
         self.widen = Widen(device, tuple(render_hw)) if widen else None
+        self.chain_dtype = dtype if widen else self.dtype                  # what the last stage writes
+        self.lut = Lut3D(device, tuple(render_hw), lut, dtype=self.chain_dtype) if lut is not None else None
         self.frame_bytes = formats.frame_bytes(*self.src_hw, in_pix_fmt) if self.plan is None else self.plan.frame_bytes
         self.frame_shape = self.src_hw + (3,) if self.plan is None else (self.frame_bytes,)
         # the stages present, each with the size of the RGB frames it writes; the last one writes the chain's input
         self.stages = [(st, hw) for st, hw in ((self.plan, self.src_hw), (self.deint, self.src_hw), (self.canvas, cut),
-                                                    (self.resize, tuple(render_hw)), (self.widen, tuple(render_hw))) if st is not None]
+                                                    (self.resize, tuple(render_hw)), (self.widen, tuple(render_hw)),
+                                                    (self.lut, tuple(render_hw))) if st is not None]
 
     def slots(self, B: int, NS: int, pinned: bool = True):
         import torch
@@ -68,8 +74,9 @@ class SourceEnd(StagingSlots):
         # a stage that is not the last one writes RGB slots of its own: a missing stage costs no buffer.  B counts source frames: the
         # Deinterlace and every stage behind it write B * ratio frames
         behind = [any(st is self.deint for st, _ in self.stages[:i + 1]) for i in range(len(self.stages))]
-        self.mid = [[torch.empty((B * (self.ratio if behind[i] else 1),) + hw + (3,), dtype=self.dtype, device=self.device) for _ in range(NS)]
-                    for i, (_, hw) in enumerate(self.stages[:-1])]
+        self.mid = [[torch.empty((B * (self.ratio if behind[i] else 1),) + hw + (3,), dtype=self.chain_dtype if st is self.widen else self.dtype,
+                                 device=self.device) for _ in range(NS)]
+                    for i, (st, hw) in enumerate(self.stages[:-1])]
         return self.adopt([torch.empty(shape, dtype=torch.uint8, device=self.device) for _ in range(NS)],
                           [torch.empty(shape, dtype=torch.uint8).pin_memory() for _ in range(NS)] if pinned else None)
 
@@ -90,14 +97,19 @@ class DeliveryEnd:
     Canvas is built and the stages are those of "stretch".  `narrow` is None or a dither name of depth.DITHERS: the chain runs on half
     pixels and the delivery is an 8-bit one, so behind the geometry, which runs on the half frames, a Narrow at the delivery size
     (include/crtfx_depth.h) writes the uint8 frames the egress plan reads — or, for "rgb24", the frames that are downloaded; the dither's
-    coordinates are those of the delivered frame.  Everything downstream is in frames of `frame_bytes`, batches of `shape(B)`."""
+    coordinates are those of the delivered frame.  `lut` is None or a Cube: a Lut3D (include/crtfx_lut3d.h) at the render size and on
+    `pix` is then the FIRST stage, in front of the delivery resize, the Canvas, the Narrow and the egress plan — a pad colour is not
+    transformed and the dither stays last.  Everything downstream is in frames of `frame_bytes`, batches of `shape(B)`."""
 
     def __init__(self, device, render_hw, pix, out_pix_fmt, out_matrix, out_range, out_chroma, deliver, deliver_filter,
-                 deliver_fit="stretch", pad_color=(0, 0, 0), narrow=None):
+                 deliver_fit="stretch", pad_color=(0, 0, 0), narrow=None, lut=None):
         self.device, self.pix = device, pix
         self.size = tuple(deliver) if deliver is not None else tuple(render_hw)
-        self.resize = self.canvas = self.narrow = None
+        self.resize = self.canvas = self.narrow = self.lut = None
         self.stages = []                 # (plan, the size of the frames it writes), in order, in front of the egress plan
+        if lut is not None:
+            self.lut = Lut3D(device, tuple(render_hw), lut, dtype=pix)
+            self.stages.append((self.lut, tuple(render_hw)))
         inner, at = fit_pad(render_hw, self.size) if deliver is not None and deliver_fit == "pad" else (self.size, (0, 0))
         window = fit_crop(render_hw, self.size) if deliver is not None and deliver_fit == "crop" else (0, 0) + tuple(render_hw)
         if inner != self.size:

@@ -150,7 +150,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                    in_filter: str = "bilinear", deliver_filter: str = "bilinear", in_crop: Optional[Tuple[int, int, int, int]] = None,
                    deliver_fit: str = "stretch", deliver_pad_color: Tuple[int, int, int] = (0, 0, 0), chain_pix: str = "auto",
                    dither: str = "none", deinterlace: str = "off", field_order: str = "tff", deinterlace_fields: str = "first",
-                   **io_keywords) -> int:
+                   in_lut=None, deliver_lut=None, **io_keywords) -> int:
     """Render every frame of `frame_iter` (H x W x 3 uint8 RGB arrays) and hand the finished uint8 frames to `write_frame` in order.
     Effect keywords: the names, meaning and defaults of process_video / the CLI (ref:864-911, :1155-1206); the caller applies the clamps of
     ref:1225-1266 as the reference's `main` does (`pythoncrt_amd.cli.settings_from_args` restates them).  Returns the number of frames written.
@@ -255,6 +255,19 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     stage; 4:2:2, 4:4:4 and rgb24 sources have no such pairing.  Refused with ValueError before a device is touched: an unknown value of
     the three keywords; `field_order` or `deinterlace_fields` off its default with "off" (there is nothing to deinterlace);
     `resize_on="host"`; a source height below 2 where it is known (`in_size`, or the render size for a packed `in_pix_fmt`).
+    `in_lut` / `deliver_lut` put a 3D colour LUT directly in front of the chain and directly behind it: a path to a `.cube` file or a
+    `pythoncrt_amd.cube.Cube`, applied on the device with tetrahedral interpolation (Lut3D, include/crtfx_lut3d.h) at render size and on
+    the chain's pixel type — what `lut3d=` in a second ffmpeg process did.  `in_lut` is the source end's last stage, behind the resize
+    and behind the Widen of `chain_pix="half"`: a log-encoded camera source (ProRes 4444 / DNxHR 444 decodes) or an HDR10 one becomes
+    display-referred video before the tube sees it, and an 8-bit log source on a half chain is transformed at half precision; every
+    source then goes through a source end, an rgb24 frame at render size through one whose only stage is the LUT.  `deliver_lut` is the
+    delivery end's first stage, in front of the delivery resize, the Canvas, the Narrow and the egress plan: a look or display
+    transform on the finished frames; a pad colour is not transformed and the dither stays last.  HDR10 to SDR, with a PQ / BT.2020 ->
+    BT.709 cube of the user's: `in_pix_fmt="p010le", in_lut="pq2020_to_709.cube"` (with `chain_pix="half"` for an 8-bit delivery).
+    Stated limit: the cube's entries and the results are quarter codes (0..1020 for 0..255), so a cube's precision is 10 bits, and only the
+    domain 0..1 and sizes 2..65 are taken.  `None` (default) creates no plan and no buffer: the path as it was.  Refused with ValueError
+    before a device is touched: a cube that cannot be read or is malformed (the message names the file and the line), a value that is
+    neither a path nor a Cube, and `in_lut` with `resize_on="host"`.
     If `frame_iter` or `write_frame` raises, the GPU work already queued is drained (device synchronize) before the exception leaves this
     function, so that the staging buffers are not freed under a running copy."""
     import os
@@ -337,6 +350,11 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                          "resize to filter")
     if deliver_fit != "stretch" and deliver is None:
         raise ValueError(f"deliver_fit={deliver_fit!r} without a deliver_size that differs from the render size: there is nothing to fit")
+    from .cube import as_cube
+    if in_lut is not None and resize_on == "host":
+        raise ValueError("resize_on='host' cannot be combined with in_lut: the cube is applied on the device, behind the device's resize")
+    in_cube = as_cube(in_lut, "in_lut") if in_lut is not None else None
+    deliver_cube = as_cube(deliver_lut, "deliver_lut") if deliver_lut is not None else None
     if not torch.cuda.is_available():
         raise RuntimeError("no ROCm device visible; pythoncrt_amd has no CPU fallback")
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -365,9 +383,9 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     total = max(1, int(total_frames)) if total_frames else None
 
     NS = 2
-    pin_in = [torch.empty((B, h, w, 3), dtype=torch.uint8).pin_memory() for _ in range(NS)] if in_pix_fmt == "rgb24" and not widen and deint is None else None   # else: a SourceEnd's own
+    pin_in = [torch.empty((B, h, w, 3), dtype=torch.uint8).pin_memory() for _ in range(NS)] if in_pix_fmt == "rgb24" and not widen and deint is None and in_cube is None else None   # else: a SourceEnd's own
     end = DeliveryEnd(dev, (h, w), pix, out_pix_fmt, out_matrix, out_range, out_chroma, deliver, deliver_filter, deliver_fit, pad_color,
-                      narrow=narrow)
+                      narrow=narrow, **({} if deliver_cube is None else {"lut": deliver_cube}))
     pin_out = [torch.empty(end.shape(B), dtype=torch.uint8).pin_memory() for _ in range(NS)]    # what is downloaded and handed to the writer
     dev_in = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]
     dev_out = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]
@@ -394,7 +412,8 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                 torch.cuda.synchronize(dev)
                 sources.pop(next(iter(sources)))
             fmt, hw = (in_pix_fmt, yuv_hw) if key == YUV else ("rgb24", key)
-            src = SourceEnd(dev, (h, w), fmt, in_matrix, in_range, in_chroma, hw, in_filter, crop, pix, widen=widen, deinterlace=deint).slots(Bs, NS)
+            src = SourceEnd(dev, (h, w), fmt, in_matrix, in_range, in_chroma, hw, in_filter, crop, pix, widen=widen, deinterlace=deint,
+                            **({} if in_cube is None else {"lut": in_cube})).slots(Bs, NS)
             assert key != YUV or src.frame_bytes == yuv_bytes
         sources[key] = src
         return src
@@ -422,7 +441,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                 return a, (int(a.shape[0]), int(a.shape[1]))
             from PIL import Image
             a = np.asarray(Image.fromarray(np.ascontiguousarray(a, dtype=np.uint8)).resize((w, h), getattr(Image, in_filter.upper())))
-        return a, ((h, w) if widen or deint is not None else None)              # a half chain, a deinterlaced source: no direct upload, the frame goes through a source end
+        return a, ((h, w) if widen or deint is not None or in_cube is not None else None)      # a half chain, a deinterlaced source, an in_lut: no direct upload, the frame goes through a source end
 
     def drain(p):
         nonlocal written
