@@ -15,6 +15,7 @@
     from pythoncrt_amd import Canvas              # crop and pad: a window of uint8 or half frames placed on a canvas of another size, the rest a colour
     from pythoncrt_amd import Widen, Narrow       # format=: uint8 frames to half exactly, half frames to uint8 rounded or with ordered dither
     from pythoncrt_amd import Deinterlace         # yadif's place: two fields woven into a frame become one progressive frame, or one per field
+    from pythoncrt_amd import AdaptiveDeinterlace # ... motion-adaptive: the other field woven in where the picture stood still, "edge" where it moved
     from pythoncrt_amd import Lut3D, Cube         # lut3d=: a .cube colour LUT applied with tetrahedral interpolation, uint8 or half frames
 
 See DESIGN.md (path, kernels, roofline) and INTEGRATION.md (how the reference binds to it).
@@ -24,6 +25,7 @@ from .effects import (DeviceState, TriadMask, VignetteMask, apply_crt_effect, ap
 from .canvas import Canvas
 from .deep import EgressYuv10, UnpackYuv10
 from .depth import Narrow, Widen
+from .adeint import AdaptiveDeinterlace
 from .deint import Deinterlace
 from .deep444 import EgressDeep444, UnpackDeep444
 from .egress import EgressYuv
@@ -39,4 +41,4 @@ from .yuv422 import EgressYuv422, UnpackYuv422
 
 __all__ = ["DeviceState", "TriadMask", "VignetteMask", "apply_crt_effect", "apply_static_effects", "make_triad_mask", "make_vignette",
            "process_frames", "iter_rgb24", "iter_yuv420", "IngestResize", "EgressYuv", "UnpackYuv", "EgressYuv10", "UnpackYuv10",
-           "iter_yuv422", "EgressYuv422", "UnpackYuv422", "iter_deep444", "EgressDeep444", "UnpackDeep444", "UnpackSited", "EgressSited", "ResizeHalf", "Resample", "Canvas", "Widen", "Narrow", "Deinterlace", "Lut3D", "Cube"]
+           "iter_yuv422", "EgressYuv422", "UnpackYuv422", "iter_deep444", "EgressDeep444", "UnpackDeep444", "UnpackSited", "EgressSited", "ResizeHalf", "Resample", "Canvas", "Widen", "Narrow", "Deinterlace", "AdaptiveDeinterlace", "Lut3D", "Cube"]

@@ -79,7 +79,10 @@ geometry, and `--dither ordered` adds an 8 x 8 Bayer threshold there instead of 
 `--deinterlace linear|edge` takes every input frame as two woven fields and deinterlaces it on the GPU before anything else sees it
 (include/crtfx_deint.h), `--field-order tff|bff` says which field comes first, and `--deinterlace-fields both` writes one frame per FIELD:
 the chain then runs at field rate and `--persistence` decays field to field, as phosphor does.  Pass the field rate as `--fps`; the output
-holds twice the input's frames.  A 480i uyvy422 capture sent as fields, no host `yadif` in front of the tool:
+holds twice the input's frames.  `--deinterlace adaptive` is motion-adaptive (include/crtfx_adeint.h): where the picture did not change
+since the previous input frame the missing rows are the other field's own (HUDs, text and backgrounds keep their full vertical resolution
+and do not bob), where it changed they are `edge`'s; it looks one frame back only, so it adds no latency.
+A 480i uyvy422 capture sent as fields, no host `yadif` in front of the tool:
 
     ffmpeg -i capture_480i.avi -f rawvideo -pix_fmt uyvy422 - |
       python -m pythoncrt_amd.cli --input - --width 720 --height 480 --fps 60 --output - --in-pix-fmt uyvy422 \
@@ -328,10 +331,12 @@ def add_input_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--in-crop-y", type=int, default=0, help="top row of the window (see --in-crop-x)")
     p.add_argument("--in-crop-width", type=int, default=0, help="width of the window (see --in-crop-x); 0 (default) = no crop")
     p.add_argument("--in-crop-height", type=int, default=0, help="height of the window (see --in-crop-x); 0 (default) = no crop")
-    p.add_argument("--deinterlace", type=str, default="off", choices=["off", "linear", "edge"],
+    p.add_argument("--deinterlace", type=str, default="off", choices=["off", "linear", "edge", "adaptive"],
                    help="take every input frame as two fields woven into its even and odd rows and deinterlace it on the GPU, in front of the crop "
                         "and the resize (include/crtfx_deint.h): the rows between a field's rows are the mean of the rows above and below (linear) "
-                        "or of two of their pixels along the best of five directions per pixel (edge); off (default) = a progressive input")
+                        "or of two of their pixels along the best of five directions per pixel (edge); adaptive (include/crtfx_adeint.h) keeps the "
+                        "other field's rows where the picture did not change since the previous frame and takes edge's where it did; off (default) "
+                        "= a progressive input")
     p.add_argument("--field-order", type=str, default="tff", choices=["tff", "bff"],
                    help="which field of an interlaced input comes first: the even rows (tff, default) or the odd rows (bff); needs --deinterlace")
     p.add_argument("--deinterlace-fields", type=str, default="first", choices=["first", "both"],
@@ -349,7 +354,7 @@ def deinterlace_from_args(a):
     method, order, fields = getattr(a, "deinterlace", "off"), getattr(a, "field_order", "tff"), getattr(a, "deinterlace_fields", "first")
     if method == "off":
         if order != "tff" or fields != "first":
-            raise SystemExit(f"--field-order {order} / --deinterlace-fields {fields} without --deinterlace linear | edge: there is nothing to deinterlace")
+            raise SystemExit(f"--field-order {order} / --deinterlace-fields {fields} without --deinterlace linear | edge | adaptive: there is nothing to deinterlace")
         return None
     return method, order, fields
 
@@ -623,6 +628,8 @@ def feed(pipe, source, end, reader, writer, NS: int, fout, timed: bool):
     ratio = 1 if source is None else source.ratio
     B = Bs * ratio
     reader.start()
+    if source is not None:
+        source.restart()                                            # a new stream: --deinterlace adaptive starts without a previous frame
     dev_in, dev_out = ([torch.empty((B, pipe.h, pipe.w, 3), dtype=pipe.dtype, device=dev) for _ in range(NS)] for _ in range(2))
     dev_recv = dev_in if source is None else source.slots(Bs, NS, pinned=False).dev        # what is uploaded
     end.slots(dev_out)                                              # what the egress plan reads, what is downloaded

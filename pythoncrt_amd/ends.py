@@ -2,6 +2,7 @@
 
 from . import formats
 from ._stage import resize_plan
+from .adeint import METHOD as ADAPTIVE, AdaptiveDeinterlace
 from .canvas import Canvas, fit_crop, fit_pad
 from .deint import Deinterlace
 from .depth import Narrow, Widen
@@ -37,7 +38,9 @@ class SourceEnd(StagingSlots):
     source plan, the window and the resize are frames of `dtype`.  With `widen` those are uint8 frames in front of a half chain: a Widen at
     the render size (include/crtfx_depth.h) is then the last stage and writes the chain's half input — for an rgb24 frame at render size
     the only one.  `deinterlace` = (method, order, fields) puts a Deinterlace (include/crtfx_deint.h) directly behind the source plan, at
-    src_hw and on `dtype`, in front of the Canvas and the resize: a crop at an odd y, or any resize, would mix the fields.  `ratio` is the
+    src_hw and on `dtype`, in front of the Canvas and the resize: a crop at an odd y, or any resize, would mix the fields; with the method
+    "adaptive" an AdaptiveDeinterlace (include/crtfx_adeint.h) stands there instead, convert() pushes each batch behind the one before it,
+    and restart() starts a new history (the frames that follow are not the continuation of those converted before).  `ratio` is the
     frames it writes per source frame (1 without it): the staged slots hold SOURCE frames and convert(d, n, dst) writes n * ratio frames.
     `lut` is None or a Cube: a Lut3D (include/crtfx_lut3d.h) at the render size and on the CHAIN's pixel type is then the last stage,
     behind the resize and behind the Widen, and writes the chain's input — for an rgb24 frame at render size the only one."""
@@ -48,10 +51,12 @@ class SourceEnd(StagingSlots):
         self.device, self.src_hw = device, tuple(src_hw)
         self.dtype = torch.uint8 if dtype is None or widen else dtype      # widen: `dtype` is the chain's, the stages in front of it run on uint8
         self.plan = formats.source_plan(device, self.src_hw, in_pix_fmt, in_matrix, in_range, in_chroma)
-        self.deint, self.ratio = None, 1
+        self.deint, self.ratio, self.adaptive = None, 1, False
         if deinterlace is not None:
             method, order, fields = deinterlace
-            self.deint = Deinterlace(device, self.src_hw, method=method, order=order, fields=fields, dtype=self.dtype)
+            self.adaptive = method == ADAPTIVE
+            self.deint = (AdaptiveDeinterlace(device, self.src_hw, order=order, fields=fields, dtype=self.dtype) if self.adaptive else
+                          Deinterlace(device, self.src_hw, method=method, order=order, fields=fields, dtype=self.dtype))
             self.ratio = 2 if fields == "both" else 1
         self.canvas, cut = None, self.src_hw
         if crop is not None:
@@ -85,7 +90,13 @@ class SourceEnd(StagingSlots):
         for i, (stage, _) in enumerate(self.stages):
             if stage is self.deint:
                 n *= self.ratio
-            x = stage.run(x, out=dst if i == len(self.stages) - 1 else self.mid[i][d][:n])
+            run = stage.push if self.adaptive and stage is self.deint else stage.run      # the adaptive plan keeps the last frame of the batch before
+            x = run(x, out=dst if i == len(self.stages) - 1 else self.mid[i][d][:n])
+
+    def restart(self):
+        """The next batch converted does not continue the one before it: an AdaptiveDeinterlace forgets its kept frame.  Nothing otherwise."""
+        if self.adaptive:
+            self.deint.reset()
 
 
 class DeliveryEnd:

@@ -244,15 +244,20 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     consoles, camcorders, DVDs) and deinterlaces it on the device before anything else sees it: Deinterlace (include/crtfx_deint.h) stands
     directly behind the source plan, at the source size, in front of `in_crop`'s Canvas and the resize, which would mix the fields.  The
     rows of a field are kept; the rows between them are the rounded mean of the kept rows above and below ("linear") or of two pixels of
-    those rows along the best of five directions, chosen per pixel ("edge").  `field_order` "tff" (default) / "bff" says which field is the
+    those rows along the best of five directions, chosen per pixel ("edge").  `deinterlace="adaptive"` is motion-adaptive: an
+    AdaptiveDeinterlace (include/crtfx_adeint.h) stands there instead, and the rows between are the OTHER field's own rows where the
+    picture did not change since the previous source frame (still content keeps its full vertical resolution and does not bob under
+    "both"), "edge"'s where it changed.  It is causal — the previous source frame, kept on the device across batches, is all it needs;
+    the first frame of the stream, and the first frame behind a change of source size in a mixed rgb24 stream, has none and is "edge"'s.
+    `field_order` "tff" (default) / "bff" says which field is the
     first.  `deinterlace_fields="first"` (default) writes one frame per source frame, made for the first field; `"both"` writes two, one per
     field in field order — a tube showed fields, not frames, and the persistence blend then decays field to field.  Under "both" a chain
     batch of B frames is fed by B // 2 source frames, B = `batch` taken even and at least 2; frame indices, `written`, `progress_cb` and
     the return value count frames WRITTEN (pass `total_frames` as such); the chain's clock stays `fps_out` as given: pass the FIELD rate
     (59.94 for 29.97i).  Every source then goes through a source end, as under `in_crop` or `chain_pix="half"` — an rgb24 frame at render
     size too — and an rgb24 frame of fewer than 2 rows raises ValueError.  "off" (default) is the path as it was: no Deinterlace is
-    created.  Known limit: the chroma rows of a 4:2:0 source are paired by its source plan as a progressive frame's are, in front of this
-    stage; 4:2:2, 4:4:4 and rgb24 sources have no such pairing.  Refused with ValueError before a device is touched: an unknown value of
+    created.  Known limit, under every method: the chroma rows of a 4:2:0 source are paired by its source plan as a progressive frame's
+    are, in front of this stage; 4:2:2, 4:4:4 and rgb24 sources have no such pairing.  Refused with ValueError before a device is touched: an unknown value of
     the three keywords; `field_order` or `deinterlace_fields` off its default with "off" (there is nothing to deinterlace);
     `resize_on="host"`; a source height below 2 where it is known (`in_size`, or the render size for a packed `in_pix_fmt`).
     `in_lut` / `deliver_lut` put a 3D colour LUT directly in front of the chain and directly behind it: a path to a `.cube` file or a
@@ -306,7 +311,10 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         raise ValueError(f"chain_pix must be one of {', '.join(CHAIN_PIX)}, got {chain_pix!r} (dither={dither!r})")
     if dither not in DITHERS:
         raise ValueError(f"dither must be one of {', '.join(DITHERS)}, got {dither!r} (chain_pix={chain_pix!r})")
-    from .deint import FIELDS, METHODS, ORDERS
+    from .adeint import METHOD as ADAPTIVE
+    from .deint import FIELDS, ORDERS
+    from .deint import METHODS as SPATIAL
+    METHODS = SPATIAL + (ADAPTIVE,)
     if deinterlace != "off" and deinterlace not in METHODS:
         raise ValueError(f"deinterlace must be 'off' or one of {', '.join(METHODS)}, got {deinterlace!r}")
     if field_order not in ORDERS:
@@ -400,6 +408,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
 
     MAX_SOURCES = 4                  # source sizes whose staging buffers and ingest plan are kept
     sources = {}                     # (src_h, src_w) -> SourceEnd, in order of last use
+    last_key = None                  # the source key of the batch before: where it changes, a source that keeps a history starts a new one
     carry = None                     # a frame already taken from the iterator that starts the next batch (its source size differs)
     YUV = "yuv"                      # the key of the one 4:2:0 / 4:2:2 source (its size is fixed by in_size): a SourceEnd
     yuv_hw = (h, w) if in_size is None else (int(in_size[0]), int(in_size[1]))
@@ -490,6 +499,9 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                 compute.wait_event(up)
                 # dev_in[d]: its last upload (two batches ago) was awaited by `compute` then, its last readers ran on `compute`
                 m = n * ratio                        # the frames the chain runs and the writer gets: n source frames, `ratio` each
+                if key != last_key and src is not direct:
+                    src.restart()                    # deinterlace="adaptive": the frame before this batch's first is not its previous frame
+                last_key = key
                 src.convert(d, n, dev_in[d][:m])                                     # on the compute stream; nothing for `direct`
                 if down_done[d] is not None:
                     compute.wait_event(down_done[d])
