@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("CRTFX_LIB") or os.path.join(_HERE, "libcrtfx.so")   #
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = [os.path.join(CSRC, f) for f in ("crtfx.hip", "crtfx_rr.hip", "crtfx_kernels.hip.h", "crtfx_common.hip.h", "crtfx_blur.hip.h", "crtfx_point.hip.h",
                                                 "crtfx_phosphor.hip.h", "crtfx_phosphor_ct.hip.h", "crtfx_warp.hip.h", "crtfx_internal.h", "crtfx_ingest.hip",
-                                                "crtfx_egress.hip", "crtfx_unpack.hip", "crtfx_deep.hip", "crtfx_422.hip", "crtfx_444.hip", "crtfx_sited.hip", "crtfx_egress_sited.hip", "crtfx_resize16.hip", "crtfx_resample.hip", "crtfx_canvas.hip", "crtfx_depth.hip", "crtfx_deint.hip", "crtfx_adeint.hip", "crtfx_edge.hip.h", "crtfx_lut3d.hip", "crtfx_stage_host.h", "crtfx_resize_host.h")] + \
+                                                "crtfx_egress.hip", "crtfx_unpack.hip", "crtfx_deep.hip", "crtfx_422.hip", "crtfx_444.hip", "crtfx_sited.hip", "crtfx_egress_sited.hip", "crtfx_resize16.hip", "crtfx_resample.hip", "crtfx_canvas.hip", "crtfx_depth.hip", "crtfx_deint.hip", "crtfx_adeint.hip", "crtfx_edge.hip.h", "crtfx_lut3d.hip", "crtfx_stage_host.h", "crtfx_resize_host.h", "crtfx_frame_host.h")] + \
           [os.path.join(ROOT, "include", f) for f in ("crtfx.h", "crtfx_ingest.h", "crtfx_egress.h", "crtfx_unpack.h", "crtfx_deep.h", "crtfx_422.h", "crtfx_444.h", "crtfx_sited.h", "crtfx_egress_sited.h", "crtfx_resize16.h", "crtfx_resample.h", "crtfx_canvas.h", "crtfx_depth.h", "crtfx_deint.h", "crtfx_adeint.h", "crtfx_lut3d.h")]
 STAGE_UNITS = ("crtfx_ingest", "crtfx_egress", "crtfx_unpack", "crtfx_deep", "crtfx_422", "crtfx_444", "crtfx_sited", "crtfx_egress_sited", "crtfx_resize16", "crtfx_resample", "crtfx_canvas", "crtfx_depth", "crtfx_deint", "crtfx_adeint", "crtfx_lut3d")   # one object file each, beside crtfx.hip / crtfx_rr.hip
 RR_RADII = tuple(range(1, 31))      # one register-window build per radius up to 30 (crtfx_internal.h); larger radii: the split path
@@ -169,76 +169,55 @@ RESIZE16_SYMBOLS = resize_symbols("resize16")
 RESAMPLE_OPT_FORCE_GENERAL, RESAMPLE_OPT_ACC64 = 1, 2
 RESAMPLE_SYMBOLS = resize_symbols("resample")
 
-# ... and every symbol include/crtfx_canvas.h declares (the geometry stage, uint8 and half: a handle of its own, pythoncrt_amd/canvas.py; the
-# resize stages' six entry points, with a create of its own: device, pix_fmt, src_h, src_w, win_y, win_x, win_h, win_w, dst_h, dst_w, dst_y,
-# dst_x, fill[3], &plan)
-CANVAS_OPT_FORCE_GENERAL = 1
-CANVAS_SYMBOLS = {
-    "crtfx_canvas_create": (ctypes.c_int, [ctypes.c_int] * 12 + [ctypes.POINTER(ctypes.c_uint16), ctypes.POINTER(_vp)]),
-    "crtfx_canvas_destroy": (ctypes.c_int, [_vp]),
-    "crtfx_canvas_last_error": (ctypes.c_char_p, [_vp]),
-    "crtfx_canvas_run": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
-    "crtfx_canvas_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
-    "crtfx_canvas_last_plan": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t]),
-}
+def frame_symbols(family, create_args, **extra):
+    """The six entry points of one crtfx_<family>_* family of frame stages (RGB frames to RGB frames; pythoncrt_amd/_stage.py's FramePlan is
+    their caller): a create of the family's own — device, create_args..., &plan — the five every family spells the same way, and what `extra`
+    names: a further entry point, or the family's own signature of one of the five."""
+    table = {"create": (ctypes.c_int, [ctypes.c_int, *create_args, ctypes.POINTER(_vp)]),
+             "destroy": (ctypes.c_int, [_vp]),
+             "last_error": (ctypes.c_char_p, [_vp]),
+             "run": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
+             "set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
+             "last_plan": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t]),
+             **extra}
+    return {f"crtfx_{family}_{name}": sig for name, sig in table.items()}
 
-# ... and every symbol include/crtfx_depth.h declares (the depth stage, uint8 <-> half: a handle of its own, pythoncrt_amd/depth.py; the resize
-# stages' six entry points, with a create of its own: device, h, w, direction, dither, &plan)
+
+_FRAMES_OUT = (ctypes.c_int, [_vp])
+
+# ... and every symbol include/crtfx_canvas.h declares (the geometry stage, uint8 and half: a handle of its own, pythoncrt_amd/canvas.py; its
+# create: device, pix_fmt, src_h, src_w, win_y, win_x, win_h, win_w, dst_h, dst_w, dst_y, dst_x, fill[3], &plan)
+CANVAS_OPT_FORCE_GENERAL = 1
+CANVAS_SYMBOLS = frame_symbols("canvas", [ctypes.c_int] * 11 + [ctypes.POINTER(ctypes.c_uint16)])
+
+# ... and every symbol include/crtfx_depth.h declares (the depth stage, uint8 <-> half: a handle of its own, pythoncrt_amd/depth.py; its
+# create: device, h, w, direction, dither, &plan)
 DEPTH_WIDEN, DEPTH_NARROW = 0, 1
 DITHER_NONE, DITHER_ORDERED = 0, 1
 DEPTH_OPT_FORCE_GENERAL = 1
-DEPTH_SYMBOLS = {
-    "crtfx_depth_create": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.POINTER(_vp)]),
-    "crtfx_depth_destroy": (ctypes.c_int, [_vp]),
-    "crtfx_depth_last_error": (ctypes.c_char_p, [_vp]),
-    "crtfx_depth_run": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
-    "crtfx_depth_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
-    "crtfx_depth_last_plan": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t]),
-}
+DEPTH_SYMBOLS = frame_symbols("depth", [ctypes.c_int] * 4)
 
-# ... and every symbol include/crtfx_deint.h declares (the deinterlace stage, uint8 and half: a handle of its own, pythoncrt_amd/deint.py; the
-# resize stages' six entry points, with a create of its own — device, h, w, pix_fmt, method, order, fields, &plan — and frames_out)
+# ... and every symbol include/crtfx_deint.h declares (the deinterlace stage, uint8 and half: a handle of its own, pythoncrt_amd/deint.py; its
+# create — device, h, w, pix_fmt, method, order, fields, &plan — and frames_out)
 DEINT_LINEAR, DEINT_EDGE = 0, 1
 DEINT_TFF, DEINT_BFF = 0, 1
 DEINT_FIRST, DEINT_BOTH = 0, 1
 DEINT_OPT_FORCE_GENERAL = 1
-DEINT_SYMBOLS = {
-    "crtfx_deint_create": (ctypes.c_int, [ctypes.c_int] * 7 + [ctypes.POINTER(_vp)]),
-    "crtfx_deint_destroy": (ctypes.c_int, [_vp]),
-    "crtfx_deint_last_error": (ctypes.c_char_p, [_vp]),
-    "crtfx_deint_frames_out": (ctypes.c_int, [_vp]),
-    "crtfx_deint_run": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
-    "crtfx_deint_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
-    "crtfx_deint_last_plan": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t]),
-}
+DEINT_SYMBOLS = frame_symbols("deint", [ctypes.c_int] * 6, frames_out=_FRAMES_OUT)
 
 # ... and every symbol include/crtfx_adeint.h declares (the motion-adaptive deinterlace stage, uint8 and half: a handle of its own,
-# pythoncrt_amd/adeint.py; the deinterlace stage's seven entry points, with a create without a method — device, h, w, pix_fmt, order, fields,
-# &plan — and a run that takes the previous frame first; the order and field numbers are DEINT_*)
+# pythoncrt_amd/adeint.py; a create without a method — device, h, w, pix_fmt, order, fields, &plan — frames_out, and a run that takes the
+# previous frame first; the order and field numbers are DEINT_*)
 ADEINT_OPT_FORCE_GENERAL = 1
-ADEINT_SYMBOLS = {
-    "crtfx_adeint_create": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.POINTER(_vp)]),
-    "crtfx_adeint_destroy": (ctypes.c_int, [_vp]),
-    "crtfx_adeint_last_error": (ctypes.c_char_p, [_vp]),
-    "crtfx_adeint_frames_out": (ctypes.c_int, [_vp]),
-    "crtfx_adeint_run": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
-    "crtfx_adeint_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
-    "crtfx_adeint_last_plan": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t]),
-}
+ADEINT_SYMBOLS = frame_symbols("adeint", [ctypes.c_int] * 5, frames_out=_FRAMES_OUT,
+                               run=(ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]))
 
-# ... and every symbol include/crtfx_lut3d.h declares (the 3D LUT stage, uint8 and half: a handle of its own, pythoncrt_amd/lut3d.py; the resize
-# stages' six entry points, with a create of its own — device, h, w, pix_fmt, N, table, &plan — and set_table)
+# ... and every symbol include/crtfx_lut3d.h declares (the 3D LUT stage, uint8 and half: a handle of its own, pythoncrt_amd/lut3d.py; its
+# create — device, h, w, pix_fmt, N, table, &plan — and set_table)
 LUT3D_QMAX, LUT3D_MIN_N, LUT3D_MAX_N, LUT3D_LDS_MAX_N = 1020, 2, 65, 34
 LUT3D_OPT_FORCE_GENERAL, LUT3D_OPT_FORCE_GLOBAL = 1, 2
-LUT3D_SYMBOLS = {
-    "crtfx_lut3d_create": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_uint16), ctypes.POINTER(_vp)]),
-    "crtfx_lut3d_destroy": (ctypes.c_int, [_vp]),
-    "crtfx_lut3d_last_error": (ctypes.c_char_p, [_vp]),
-    "crtfx_lut3d_run": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
-    "crtfx_lut3d_set_table": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint16)]),
-    "crtfx_lut3d_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
-    "crtfx_lut3d_last_plan": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t]),
-}
+LUT3D_SYMBOLS = frame_symbols("lut3d", [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_uint16)],
+                              set_table=(ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint16)]))
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC"]
 

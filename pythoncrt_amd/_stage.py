@@ -1,9 +1,11 @@
 """What every plan object over a libcrtfx handle shares.  `Handle` is the handle of one crtfx_<family>_* family behind a plan object: device,
 create and its error path, options, the batched run, the plan string, close.  On it stand `StagePlan` — the ten format-stage plans
 (unpack.py, egress.py, deep.py, yuv422.py, deep444.py) and the two sited plans (sited.py: source and egress), seven entry points each
-(`_lib.stage_symbols`) — and `ResizePlan` — the three resize plans (ingest.py, resize16.py, resample.py), six entry points each
-(`_lib.resize_symbols`).  A family module declares short classes on `SourcePlan` / `EgressPlan` / `ResizePlan` — family name, C layout
-numbers or dtype, table function, frame size — and keeps its layout helpers; everything else is here."""
+(`_lib.stage_symbols`) — `ResizePlan` — the three resize plans (ingest.py, resize16.py, resample.py), six entry points each
+(`_lib.resize_symbols`) — and `FramePlan` — the six plans of the five frame stages (canvas.py, depth.py, deint.py, adeint.py, lut3d.py), six
+entry points and a create of its own each (`_lib.frame_symbols`).  A family module declares short classes on `SourcePlan` / `EgressPlan` /
+`ResizePlan` / `FramePlan` — family name, C layout numbers or dtype, table function, frame size, its own arguments — and keeps what is truly
+its own; everything else is here."""
 from __future__ import annotations
 
 import ctypes
@@ -56,7 +58,8 @@ class Handle:
     def force_general(self, value) -> None:
         self.set_option(self._force_option, 1 if value else 0)
 
-    def _run(self, src, dst, n):
+    def _run(self, src, dst, n, *first):
+        """crtfx_<family>_run(plan, *first, src, its stride, dst, its stride, n, stream)."""
         import torch
         for name, t in (("input", src), ("out", dst)):
             if n and not t[0].is_contiguous():
@@ -64,7 +67,7 @@ class Handle:
         if n == 0:
             return dst
         with torch.cuda.device(self.device):
-            self._check(self._fn("run")(self._plan, src.data_ptr(), src.stride(0) * src.element_size(), dst.data_ptr(),
+            self._check(self._fn("run")(self._plan, *first, src.data_ptr(), src.stride(0) * src.element_size(), dst.data_ptr(),
                                         dst.stride(0) * dst.element_size(), n, torch.cuda.current_stream(self.device).cuda_stream))
         return dst
 
@@ -202,6 +205,48 @@ class ResizePlan(Handle):
         if out.dtype != dtype or tuple(out.shape) != (n, h, w, 3) or out.device != self.device:
             raise ValueError(f"out must be {self._dtype} [{n}, {h}, {w}, 3] on {self.device}")
         return self._run(frames, out, n)
+
+
+def pix_format(dtype, error=ValueError):
+    """(torch dtype, C pixel-format number) of a frame stage's `dtype` argument: None (torch.uint8), torch.uint8 or torch.float16."""
+    import torch
+    dtype = torch.uint8 if dtype is None else dtype
+    if dtype not in (torch.uint8, torch.float16):
+        raise error(f"dtype must be torch.uint8 or torch.float16, got {dtype!r}")
+    return dtype, _lib.PIX_F16 if dtype == torch.float16 else _lib.PIX_U8
+
+
+class FramePlan(Handle):
+    """A frame stage: out = plan.run(frames[n, sh, sw, 3]) -> [n * frames_out, dh, dw, 3], either side of a dtype of its own (plan(frames)
+    is the same call).  A plan says what it takes and gives with `_frames` before it is run."""
+    frames_out = 1               # output frames per source frame
+
+    def _frames(self, takes, gives=None):
+        """(h, w, torch dtype) of one source frame and of one output frame (the same unless given)."""
+        self._takes, self._gives = tuple(takes), tuple(gives or takes)
+
+    def _check_frames(self, frames) -> int:
+        h, w, dtype = self._takes
+        name = str(dtype).replace("torch.", "")
+        if frames.dtype != dtype:
+            raise _lib.CrtfxError(_lib.E_UNSUPPORTED, f"this plan takes {name} RGB frames, got {frames.dtype}")
+        if frames.dim() != 4 or tuple(frames.shape[1:]) != (h, w, 3) or frames.device != self.device:
+            raise ValueError(f"frames must be {name} [n, {h}, {w}, 3] on {self.device}, got {tuple(frames.shape)} on {frames.device}")
+        return int(frames.shape[0])
+
+    def _check_out(self, n, out):
+        import torch
+        h, w, dtype = self._gives
+        shape = (n * self.frames_out, h, w, 3)
+        if out is None:
+            return torch.empty(shape, dtype=dtype, device=self.device)
+        if out.dtype != dtype or tuple(out.shape) != shape or out.device != self.device:
+            raise ValueError(f"out must be {str(dtype).replace('torch.', '')} {list(shape)} on {self.device}")
+        return out
+
+    def run(self, frames, out=None):
+        n = self._check_frames(frames)
+        return self._run(frames, self._check_out(n, out), n)
 
 
 def resize_plan(device, src_size, dst_size, filter="bilinear", dtype=None):     # noqa: A002 - the resize plans' keyword

@@ -9,13 +9,13 @@ from __future__ import annotations
 from typing import Tuple
 
 from . import _lib
-from ._stage import Handle
+from ._stage import FramePlan, pix_format
 from .deint import FIELDS, ORDERS
 
 METHOD = "adaptive"                 # the value of process_frames(deinterlace=) and --deinterlace that builds this plan; deint.METHODS are Deinterlace's
 
 
-class AdaptiveDeinterlace(Handle):
+class AdaptiveDeinterlace(FramePlan):
     """plan = AdaptiveDeinterlace(device, (h, w), order="tff", fields="first", dtype=None);
     out = plan.run(frames[n, h, w, 3], prev=None) -> [n * frames_out, h, w, 3] of the same dtype: source frame i gives output frame i
     ("first") or output frames 2 i and 2 i + 1 ("both").  `prev` is the [h, w, 3] frame in front of frames[0], or None: frames[0] then has no
@@ -36,39 +36,20 @@ class AdaptiveDeinterlace(Handle):
         self.frames_out = 2 if fields == "both" else 1
         self._kept, self._has_kept = None, False
         self._open(device)
-        import torch
-        self.dtype = torch.uint8 if dtype is None else dtype
-        if self.dtype not in (torch.uint8, torch.float16):
-            raise ValueError(f"dtype must be torch.uint8 or torch.float16, got {dtype!r}")
+        self.dtype, pix_fmt = pix_format(dtype)
         self.size = (int(size[0]), int(size[1]))
-        self._create(self.size[0], self.size[1], _lib.PIX_F16 if self.dtype == torch.float16 else _lib.PIX_U8, ORDERS.index(order), FIELDS.index(fields))
+        self._create(self.size[0], self.size[1], pix_fmt, ORDERS.index(order), FIELDS.index(fields))
         assert self._fn("frames_out")(self._plan) == self.frames_out
+        self._frames(self.size + (self.dtype,))
         if force_general:
             self.force_general = True
 
     def run(self, frames, out=None, prev=None):
-        import torch
         h, w = self.size
-        if frames.dtype != self.dtype:
-            raise _lib.CrtfxError(_lib.E_UNSUPPORTED, f"this plan takes {self.dtype} RGB frames, got {frames.dtype}")
-        if frames.dim() != 4 or tuple(frames.shape[1:]) != (h, w, 3) or frames.device != self.device:
-            raise ValueError(f"frames must be {self.dtype} [n, {h}, {w}, 3] on {self.device}, got {tuple(frames.shape)} on {frames.device}")
+        n = self._check_frames(frames)
         if prev is not None and (prev.dtype != self.dtype or tuple(prev.shape) != (h, w, 3) or prev.device != self.device or not prev.is_contiguous()):
             raise ValueError(f"prev must be one contiguous {self.dtype} [{h}, {w}, 3] frame on {self.device}, got {prev.dtype} {tuple(prev.shape)} on {prev.device}")
-        n = int(frames.shape[0])
-        if out is None:
-            out = torch.empty((n * self.frames_out, h, w, 3), dtype=self.dtype, device=self.device)
-        if out.dtype != self.dtype or tuple(out.shape) != (n * self.frames_out, h, w, 3) or out.device != self.device:
-            raise ValueError(f"out must be {self.dtype} [{n * self.frames_out}, {h}, {w}, 3] on {self.device}")
-        for name, t in (("input", frames), ("out", out)):
-            if n and not t[0].is_contiguous():
-                raise ValueError(f"every frame of the {name} must be contiguous (only the batch stride is free)")
-        if n == 0:
-            return out
-        with torch.cuda.device(self.device):
-            self._check(self._fn("run")(self._plan, None if prev is None else prev.data_ptr(), frames.data_ptr(), frames.stride(0) * frames.element_size(),
-                                        out.data_ptr(), out.stride(0) * out.element_size(), n, torch.cuda.current_stream(self.device).cuda_stream))
-        return out
+        return self._run(frames, self._check_out(n, out), n, None if prev is None else prev.data_ptr())
 
     def push(self, frames, out=None):
         """run() behind the frames pushed before: the previous frame is the last frame of the push before this one (none behind reset() or at

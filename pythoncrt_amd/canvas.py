@@ -8,7 +8,7 @@ import ctypes
 from typing import Optional, Tuple
 
 from . import _lib
-from ._stage import Handle
+from ._stage import FramePlan, pix_format
 
 
 def _rdiv(a: int, b: int) -> int:
@@ -36,7 +36,7 @@ def fit_crop(size: Tuple[int, int], deliver: Tuple[int, int]):
     return (h - ch) // 2, (w - cw) // 2, ch, cw
 
 
-class Canvas(Handle):
+class Canvas(FramePlan):
     """plan = Canvas(device, (src_h, src_w), (dst_h, dst_w), window=(y, x, h, w), at=(dst_y, dst_x), fill=(r, g, b));
     out = plan.run(frames[n, src_h, src_w, 3]) -> [n, dst_h, dst_w, 3] of the same dtype: the window placed at `at`, `fill` elsewhere.
     `window=None` is the whole source; `fill` is 0..255 per channel (for float16 frames the half of that value); `dtype` is torch.uint8
@@ -49,11 +49,8 @@ class Canvas(Handle):
     def __init__(self, device, src_size: Tuple[int, int], dst_size: Tuple[int, int], window: Optional[Tuple[int, int, int, int]] = None,
                  at: Tuple[int, int] = (0, 0), fill: Tuple[int, int, int] = (0, 0, 0), dtype=None, force_general: bool = False):
         import numpy as np
-        import torch
         self._open(device)
-        self.dtype = torch.uint8 if dtype is None else dtype
-        if self.dtype not in (torch.uint8, torch.float16):
-            raise _lib.CrtfxError(_lib.E_UNSUPPORTED, f"only uint8 and float16 RGB frames are moved, got {self.dtype}")
+        self.dtype, pix_fmt = pix_format(dtype, error=lambda text: _lib.CrtfxError(_lib.E_UNSUPPORTED, text))
         self.src_size = (int(src_size[0]), int(src_size[1]))
         self.dst_size = (int(dst_size[0]), int(dst_size[1]))
         self.window = (0, 0) + self.src_size if window is None else tuple(int(v) for v in window)
@@ -61,24 +58,8 @@ class Canvas(Handle):
         self.fill = tuple(int(v) for v in fill)
         if len(self.window) != 4 or len(self.fill) != 3 or min(self.fill) < 0 or max(self.fill) > 255:
             raise ValueError(f"window is (y, x, h, w) and fill three values 0..255, got {window!r} and {fill!r}")
-        half = self.dtype == torch.float16
-        codes = np.array(self.fill, dtype=np.float16).view(np.uint16) if half else np.array(self.fill, dtype=np.uint16)
-        self._create(_lib.PIX_F16 if half else _lib.PIX_U8, *self.src_size, *self.window, *self.dst_size, *self.at,
-                     (ctypes.c_uint16 * 3)(*(int(c) for c in codes)))
+        codes = np.array(self.fill, dtype=np.float16).view(np.uint16) if pix_fmt == _lib.PIX_F16 else np.array(self.fill, dtype=np.uint16)
+        self._create(pix_fmt, *self.src_size, *self.window, *self.dst_size, *self.at, (ctypes.c_uint16 * 3)(*(int(c) for c in codes)))
+        self._frames(self.src_size + (self.dtype,), self.dst_size + (self.dtype,))
         if force_general:
             self.force_general = True
-
-    def run(self, frames, out=None):
-        import torch
-        (sh, sw), (h, w) = self.src_size, self.dst_size
-        name = str(self.dtype).replace("torch.", "")
-        if frames.dtype != self.dtype:
-            raise _lib.CrtfxError(_lib.E_UNSUPPORTED, f"this plan moves {name} RGB frames, got {frames.dtype}")
-        if frames.dim() != 4 or tuple(frames.shape[1:]) != (sh, sw, 3) or frames.device != self.device:
-            raise ValueError(f"frames must be {name} [n, {sh}, {sw}, 3] on {self.device}, got {tuple(frames.shape)} on {frames.device}")
-        n = int(frames.shape[0])
-        if out is None:
-            out = torch.empty((n, h, w, 3), dtype=self.dtype, device=self.device)
-        if out.dtype != self.dtype or tuple(out.shape) != (n, h, w, 3) or out.device != self.device:
-            raise ValueError(f"out must be {name} [{n}, {h}, {w}, 3] on {self.device}")
-        return self._run(frames, out, n)

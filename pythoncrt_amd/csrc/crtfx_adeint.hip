@@ -11,7 +11,7 @@
 
 #include "crtfx_adeint.h"
 #include "crtfx_edge.hip.h"
-#include "crtfx_stage_host.h"
+#include "crtfx_frame_host.h"
 
 namespace crtfx_adeint_impl {
 
@@ -214,36 +214,16 @@ __global__ __launch_bounds__(BLOCK) void k_adeint(Args a) {
 
 using namespace crtfx_adeint_impl;
 
-struct crtfx_adeint {
-    int device = 0;
+struct crtfx_adeint : crtfx_frames::Plan {     // one frame size and sample type on both sides; frames_out = 2 under fields=both
     int h = 0, w = 0;
     bool half = false, bff = false, both = false;
-    size_t frame_bytes = 0;             // of one frame, source or output
-    bool force_general = false;
-    char plan[128] = "";
-    std::string err;
 };
 
 namespace {
 
-using crtfx_stage::DeviceGuard;
+using crtfx_frames::Batch;
 using crtfx_stage::create_err;
 using crtfx_stage::fail;
-
-using H = crtfx_adeint;
-
-// the vec kernels' conditions (crtfx_adeint.h); n counts source frames
-bool vec_fits(const H* p, const void* prev, const void* src, size_t src_stride, const void* dst, size_t dst_stride, int n) {
-    if (p->force_general || (p->w & 7)) return false;
-    if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(prev)) & 3u) return false;
-    if (n > 1 && (src_stride & 3u)) return false;
-    return (size_t)n * (p->both ? 2 : 1) <= 1 || !(dst_stride & 3u);
-}
-
-void note_plan(H* p, bool fits, int frames) {
-    snprintf(p->plan, sizeof p->plan, "adeint=k_adeint<%s,%s,%s>;frames=%d", p->half ? f16::name : u8::name, p->both ? both::name : first::name,
-             fits ? vec::name : general::name, frames);
-}
 
 template <class P, class F>
 void launch_path(bool fits, dim3 grid, hipStream_t st, const Args& a) {
@@ -252,104 +232,82 @@ void launch_path(bool fits, dim3 grid, hipStream_t st, const Args& a) {
 }
 
 template <class P>
-void launch_fields(const H* p, bool fits, dim3 grid, hipStream_t st, const Args& a) {
+void launch_fields(const crtfx_adeint* p, bool fits, dim3 grid, hipStream_t st, const Args& a) {
     if (p->both) launch_path<P, both>(fits, grid, st, a); else launch_path<P, first>(fits, grid, st, a);
 }
+
+struct U : crtfx_frames::Unit {
+    using H = crtfx_adeint;
+    static constexpr int force_option = CRTFX_ADEINT_OPT_FORCE_GENERAL;
+    static constexpr const char* name = "adeint";
+    static constexpr bool one_size = true;
+
+    // the vec kernels' conditions (crtfx_adeint.h); b.n counts source frames
+    static bool vec_fits(const H* p, const Batch& b) {
+        if (p->force_general || (p->w & 7)) return false;
+        if ((reinterpret_cast<uintptr_t>(b.src) | reinterpret_cast<uintptr_t>(b.dst) | reinterpret_cast<uintptr_t>(b.prev)) & 3u) return false;
+        if (b.n > 1 && (b.src_stride & 3u)) return false;
+        return (size_t)b.n * p->frames_out <= 1 || !(b.dst_stride & 3u);
+    }
+
+    static void note_plan(H* p, bool fits, int frames) {
+        snprintf(p->plan, sizeof p->plan, "adeint=k_adeint<%s,%s,%s>;frames=%d", p->half ? f16::name : u8::name, p->both ? both::name : first::name,
+                 fits ? vec::name : general::name, frames);
+    }
+
+    static Args make_args(const H* p, bool, const Batch& b) {
+        Args a{};
+        a.prev = static_cast<const uint8_t*>(b.prev);
+        a.h = (uint32_t)p->h; a.w = (uint32_t)p->w;
+        a.blocks_row = a.w / 8u;
+        a.lanes = a.h * a.blocks_row;                                   // below 2^27
+        a.first = p->bff ? 1u : 0u;
+        return a;
+    }
+
+    static void launch(const H* p, bool fits, Args& a, int f, unsigned g, hipStream_t st) {
+        if (f) a.prev = a.src - a.src_stride;                           // a later group: the last frame of the group before it
+        const dim3 grid = fits ? dim3((a.lanes + BLOCK - 1) / BLOCK, 1, g) : dim3((a.w + BLOCK - 1) / BLOCK, p->h, g);
+        if (p->half) launch_fields<f16>(p, fits, grid, st, a); else launch_fields<u8>(p, fits, grid, st, a);
+    }
+};
 
 }  // namespace
 
 extern "C" {
 
-const char* crtfx_adeint_last_error(const crtfx_adeint* p) { return p ? p->err.c_str() : create_err<H>().c_str(); }
+const char* crtfx_adeint_last_error(const crtfx_adeint* p) { return p ? p->err.c_str() : create_err<crtfx_adeint>().c_str(); }
 
 int crtfx_adeint_create(int device, int h, int w, int pix_fmt, int order, int fields, crtfx_adeint** out_plan) {
-    create_err<H>().clear();
-    if (!out_plan) return fail<H>(nullptr, CRTFX_E_INVALID, "out_plan is null");
-    *out_plan = nullptr;
+    using H = crtfx_adeint;
+    if (const int rc = crtfx_frames::begin_create(out_plan)) return rc;
     if (h < 2 || h > 32767) return fail<H>(nullptr, CRTFX_E_INVALID, "h = %d outside 2..32767 (a frame of two fields has two rows)", h);
-    if (w < 1 || w > 32767) return fail<H>(nullptr, CRTFX_E_INVALID, "w = %d outside 1..32767", w);
+    if (const int rc = crtfx_frames::check_size<H>("w", w)) return rc;
     if (pix_fmt != CRTFX_PIX_U8 && pix_fmt != CRTFX_PIX_F16) return fail<H>(nullptr, CRTFX_E_INVALID, "unknown pix_fmt %d", pix_fmt);
     if (order != CRTFX_DEINT_TFF && order != CRTFX_DEINT_BFF) return fail<H>(nullptr, CRTFX_E_INVALID, "unknown order %d", order);
     if (fields != CRTFX_DEINT_FIRST && fields != CRTFX_DEINT_BOTH) return fail<H>(nullptr, CRTFX_E_INVALID, "unknown fields %d", fields);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail<H>(nullptr, CRTFX_E_HIP, "no HIP device %d", device);
-    DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return fail<H>(nullptr, CRTFX_E_HIP, "hipSetDevice(%d): %s", device, hipGetErrorString(guard.err));
-    H* p = new (std::nothrow) H();
-    if (!p) return fail<H>(nullptr, CRTFX_E_NOMEM, "out of host memory");
-    p->device = device; p->h = h; p->w = w;
-    p->half = pix_fmt == CRTFX_PIX_F16; p->bff = order == CRTFX_DEINT_BFF; p->both = fields == CRTFX_DEINT_BOTH;
-    p->frame_bytes = (size_t)h * w * 3 * (p->half ? 2 : 1);
-    note_plan(p, vec_fits(p, nullptr, nullptr, 0, nullptr, 0, 1), 0);
-    *out_plan = p;
-    return CRTFX_OK;
+    return crtfx_frames::new_plan<U>(device, out_plan, [&](H* p) {
+        p->h = h; p->w = w;
+        p->half = pix_fmt == CRTFX_PIX_F16; p->bff = order == CRTFX_DEINT_BFF; p->both = fields == CRTFX_DEINT_BOTH;
+        p->src_bps = p->dst_bps = p->half ? 2 : 1;
+        p->src_bytes = p->dst_bytes = (size_t)h * w * 3 * p->src_bps;
+        p->frames_out = p->both ? 2 : 1;
+        return CRTFX_OK;
+    });
 }
 
-int crtfx_adeint_frames_out(const crtfx_adeint* p) { return !p ? 0 : p->both ? 2 : 1; }
+int crtfx_adeint_frames_out(const crtfx_adeint* p) { return p ? p->frames_out : 0; }
 
-int crtfx_adeint_destroy(crtfx_adeint* p) {
-    if (!p) return CRTFX_OK;
-    DeviceGuard guard(p->device);
-    (void)hipDeviceSynchronize();
-    delete p;
-    return CRTFX_OK;
-}
+int crtfx_adeint_destroy(crtfx_adeint* p) { return crtfx_frames::destroy(p); }
 
-int crtfx_adeint_set_option(crtfx_adeint* p, int option, int value) {
-    if (!p) return CRTFX_E_INVALID;
-    if (option != CRTFX_ADEINT_OPT_FORCE_GENERAL) return fail(p, CRTFX_E_INVALID, "unknown adeint option %d", option);
-    if (value != 0 && value != 1) return fail(p, CRTFX_E_INVALID, "FORCE_GENERAL takes 0 or 1, got %d", value);
-    p->force_general = value != 0;
-    note_plan(p, vec_fits(p, nullptr, nullptr, 0, nullptr, 0, 1), 0);
-    return CRTFX_OK;
-}
+int crtfx_adeint_set_option(crtfx_adeint* p, int option, int value) { return crtfx_frames::set_option<U>(p, option, value); }
 
-int crtfx_adeint_last_plan(crtfx_adeint* p, char* buf, size_t n) {
-    if (!p || !buf || n == 0) return CRTFX_E_INVALID;
-    snprintf(buf, n, "%s", p->plan);
-    return CRTFX_OK;
-}
+int crtfx_adeint_last_plan(crtfx_adeint* p, char* buf, size_t n) { return crtfx_frames::last_plan(p, buf, n); }
 
 int crtfx_adeint_run(crtfx_adeint* p, const void* prev_frame, const void* src_base, size_t src_stride_bytes, void* dst_base, size_t dst_stride_bytes,
                      int n, void* stream) {
-    if (!p) return CRTFX_E_INVALID;
-    if (n < 0) return fail(p, CRTFX_E_INVALID, "n = %d frames", n);
-    if (n == 0) { note_plan(p, vec_fits(p, prev_frame, src_base, src_stride_bytes, dst_base, dst_stride_bytes, 0), 0); return CRTFX_OK; }
-    if (!src_base || !dst_base) return fail(p, CRTFX_E_INVALID, "null frame pointer");
-    const size_t n_out = (size_t)n * (p->both ? 2 : 1);
-    const uintptr_t sb = reinterpret_cast<uintptr_t>(src_base), db = reinterpret_cast<uintptr_t>(dst_base), pb = reinterpret_cast<uintptr_t>(prev_frame);
-    if (p->half && (((sb | db) & 1u) || (n > 1 && (src_stride_bytes & 1u)) || (n_out > 1 && (dst_stride_bytes & 1u))))
-        return fail(p, CRTFX_E_INVALID, "half frames need even bases and strides");
-    if (p->half && (pb & 1u)) return fail(p, CRTFX_E_INVALID, "half frames need an even prev_frame");
-    if ((n > 1 && src_stride_bytes < p->frame_bytes) || (n_out > 1 && dst_stride_bytes < p->frame_bytes))
-        return fail(p, CRTFX_E_INVALID, "frame strides %zu / %zu bytes are smaller than a frame (%zu)", src_stride_bytes, dst_stride_bytes, p->frame_bytes);
-    const uintptr_t se = sb + (size_t)(n - 1) * src_stride_bytes + p->frame_bytes, de = db + (n_out - 1) * dst_stride_bytes + p->frame_bytes;
-    if (sb < de && db < se) return fail(p, CRTFX_E_INVALID, "source and destination overlap");
-    if (prev_frame && pb < de && db < pb + p->frame_bytes) return fail(p, CRTFX_E_INVALID, "prev_frame and destination overlap");
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(p, CRTFX_E_HIP, "hipGetDevice failed");
-    if (dev != p->device) return fail(p, CRTFX_E_INVALID, "current device %d is not the plan's device %d (call hipSetDevice first)", dev, p->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool fits = vec_fits(p, prev_frame, src_base, src_stride_bytes, dst_base, dst_stride_bytes, n);
-    Args a{};
-    a.src_stride = src_stride_bytes; a.dst_stride = dst_stride_bytes;
-    a.h = (uint32_t)p->h; a.w = (uint32_t)p->w;
-    a.blocks_row = a.w / 8u;
-    a.lanes = a.h * a.blocks_row;                                       // below 2^27
-    a.first = p->bff ? 1u : 0u;
-    const int group = 32768;                                            // grid.z: source frames per launch
-    for (int f = 0; f < n; f += group) {
-        const unsigned g = n - f < group ? n - f : group;
-        a.src = static_cast<const uint8_t*>(src_base) + (size_t)f * src_stride_bytes;
-        a.prev = f ? a.src - src_stride_bytes : static_cast<const uint8_t*>(prev_frame);      // a later group: the last frame of the group before it
-        a.dst = static_cast<uint8_t*>(dst_base) + (size_t)f * (p->both ? 2 : 1) * dst_stride_bytes;
-        const dim3 grid = fits ? dim3((a.lanes + BLOCK - 1) / BLOCK, 1, g) : dim3((a.w + BLOCK - 1) / BLOCK, p->h, g);
-        if (p->half) launch_fields<f16>(p, fits, grid, st, a); else launch_fields<u8>(p, fits, grid, st, a);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(p, CRTFX_E_HIP, "adeint launch: %s", hipGetErrorString(e));
-    }
-    note_plan(p, fits, n);
-    return CRTFX_OK;
+    return crtfx_frames::run<U>(p, Batch{prev_frame, src_base, src_stride_bytes, dst_base, dst_stride_bytes, n}, stream);
 }
 
 }  // extern "C"
+

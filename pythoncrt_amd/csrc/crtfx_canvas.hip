@@ -7,7 +7,7 @@
 #include <type_traits>
 
 #include "crtfx_canvas.h"
-#include "crtfx_stage_host.h"
+#include "crtfx_frame_host.h"
 
 namespace crtfx_canvas_impl {
 
@@ -182,69 +182,79 @@ __global__ __launch_bounds__(BLOCK) void k_canvas(Args a) {
 
 using namespace crtfx_canvas_impl;
 
-struct crtfx_canvas {
-    int device = 0;
-    int bps = 1;                        // bytes per sample
+struct crtfx_canvas : crtfx_frames::Plan {     // src_bps == dst_bps
     int src_h = 0, src_w = 0, win_y = 0, win_x = 0, win_h = 0, win_w = 0, dst_h = 0, dst_w = 0, dst_y = 0, dst_x = 0;
     uint16_t fill[3] = {0, 0, 0};
-    size_t src_bytes = 0, dst_bytes = 0;      // of one frame
-    bool force_general = false;
-    char plan[128] = "";
-    std::string err;
 };
 
 namespace {
 
-using crtfx_stage::DeviceGuard;
+using crtfx_frames::Batch;
 using crtfx_stage::create_err;
 using crtfx_stage::fail;
 
-using H = crtfx_canvas;
+struct U : crtfx_frames::Unit {
+    using H = crtfx_canvas;
+    static constexpr int force_option = CRTFX_CANVAS_OPT_FORCE_GENERAL;
+    static constexpr const char* name = "canvas";
 
-// the vec kernel's conditions (crtfx_canvas.h)
-bool vec_fits(const H* p, const void* dst, size_t dst_stride, int n) {
-    if (p->force_general || (p->dst_bytes & 3u) || p->dst_bytes >= (1ull << 31) || p->src_bytes >= (1ull << 31)) return false;
-    if (reinterpret_cast<uintptr_t>(dst) & 3u) return false;
-    return n <= 1 || !(dst_stride & 3u);
-}
+    // the vec kernel's conditions (crtfx_canvas.h)
+    static bool vec_fits(const H* p, const Batch& b) {
+        if (p->force_general || (p->dst_bytes & 3u) || p->dst_bytes >= (1ull << 31) || p->src_bytes >= (1ull << 31)) return false;
+        if (reinterpret_cast<uintptr_t>(b.dst) & 3u) return false;
+        return b.n <= 1 || !(b.dst_stride & 3u);
+    }
 
-void note_plan(H* p, bool vec, int frames) {
-    snprintf(p->plan, sizeof p->plan, "canvas=k_canvas<%s,%s>;frames=%d", p->bps == 2 ? f16::name : u8::name, vec ? "vec" : "general", frames);
-}
+    static void note_plan(H* p, bool vec, int frames) {
+        snprintf(p->plan, sizeof p->plan, "canvas=k_canvas<%s,%s>;frames=%d", p->src_bps == 2 ? f16::name : u8::name, vec ? "vec" : "general", frames);
+    }
 
-Args make_args(const H* p, bool vec) {
-    Args a{};
-    const uint32_t unit = vec ? 3u * p->bps : 3u;                      // units per pixel
-    a.src_row = p->src_w * unit; a.dst_row = p->dst_w * unit;
-    a.src_len = vec ? (uint32_t)p->src_bytes : 0; a.dst_len = vec ? (uint32_t)p->dst_bytes : 0;
-    a.wx0 = p->dst_x * unit; a.wx1 = (p->dst_x + p->win_w) * unit; a.sx = p->win_x * unit;
-    a.win_y = p->win_y; a.win_h = p->win_h; a.dst_y = p->dst_y;
-    uint8_t bytes[12];                                                 // two pixels of half, four of uint8: twelve bytes either way
-    for (int i = 0; i < 12; ++i)
-        bytes[i] = p->bps == 2 ? (uint8_t)(p->fill[(i / 2) % 3] >> (8 * (i & 1))) : (uint8_t)p->fill[i % 3];
-    a.pat0 = bytes[0] | bytes[1] << 8 | bytes[2] << 16 | (uint32_t)bytes[3] << 24;
-    a.pat1 = bytes[4] | bytes[5] << 8 | bytes[6] << 16 | (uint32_t)bytes[7] << 24;
-    a.pat2 = bytes[8] | bytes[9] << 8 | bytes[10] << 16 | (uint32_t)bytes[11] << 24;
-    for (int c = 0; c < 3; ++c) a.fill[c] = p->fill[c];
-    return a;
-}
+    static Args make_args(const H* p, bool vec, const Batch& b) {
+        Args a{};
+        const uint32_t unit = vec ? 3u * p->src_bps : 3u;               // units per pixel
+        a.src_row = p->src_w * unit; a.dst_row = p->dst_w * unit;
+        a.src_len = vec ? (uint32_t)p->src_bytes : 0; a.dst_len = vec ? (uint32_t)p->dst_bytes : 0;
+        a.wx0 = p->dst_x * unit; a.wx1 = (p->dst_x + p->win_w) * unit; a.sx = p->win_x * unit;
+        a.win_y = p->win_y; a.win_h = p->win_h; a.dst_y = p->dst_y;
+        uint8_t bytes[12];                                              // two pixels of half, four of uint8: twelve bytes either way
+        for (int i = 0; i < 12; ++i)
+            bytes[i] = p->src_bps == 2 ? (uint8_t)(p->fill[(i / 2) % 3] >> (8 * (i & 1))) : (uint8_t)p->fill[i % 3];
+        a.pat0 = bytes[0] | bytes[1] << 8 | bytes[2] << 16 | (uint32_t)bytes[3] << 24;
+        a.pat1 = bytes[4] | bytes[5] << 8 | bytes[6] << 16 | (uint32_t)bytes[7] << 24;
+        a.pat2 = bytes[8] | bytes[9] << 8 | bytes[10] << 16 | (uint32_t)bytes[11] << 24;
+        for (int c = 0; c < 3; ++c) a.fill[c] = p->fill[c];
+        a.wide = !(reinterpret_cast<uintptr_t>(b.dst) & 15u) && (b.n <= 1 || !(b.dst_stride & 15u));
+        return a;
+    }
+
+    static void launch(const H* p, bool fits, Args& a, int, unsigned g, hipStream_t st) {
+        if (fits) {
+            const dim3 grid((unsigned)((p->dst_bytes + 16u * BLOCK - 1) / (16u * BLOCK)), 1, g);
+            if (p->src_bps == 2) hipLaunchKernelGGL((k_canvas<f16, vec>), grid, dim3(BLOCK), 0, st, a);
+            else hipLaunchKernelGGL((k_canvas<u8, vec>), grid, dim3(BLOCK), 0, st, a);
+        } else {
+            const dim3 grid((a.dst_row + BLOCK - 1) / BLOCK, p->dst_h, g);
+            if (p->src_bps == 2) hipLaunchKernelGGL((k_canvas<f16, general>), grid, dim3(BLOCK), 0, st, a);
+            else hipLaunchKernelGGL((k_canvas<u8, general>), grid, dim3(BLOCK), 0, st, a);
+        }
+    }
+};
 
 }  // namespace
 
 extern "C" {
 
-const char* crtfx_canvas_last_error(const crtfx_canvas* p) { return p ? p->err.c_str() : create_err<H>().c_str(); }
+const char* crtfx_canvas_last_error(const crtfx_canvas* p) { return p ? p->err.c_str() : create_err<crtfx_canvas>().c_str(); }
 
 int crtfx_canvas_create(int device, int pix_fmt, int src_h, int src_w, int win_y, int win_x, int win_h, int win_w,
                         int dst_h, int dst_w, int dst_y, int dst_x, const uint16_t fill[3], crtfx_canvas** out_plan) {
-    create_err<H>().clear();
-    if (!out_plan) return fail<H>(nullptr, CRTFX_E_INVALID, "out_plan is null");
-    *out_plan = nullptr;
+    using H = crtfx_canvas;
+    if (const int rc = crtfx_frames::begin_create(out_plan)) return rc;
     if (pix_fmt != CRTFX_PIX_U8 && pix_fmt != CRTFX_PIX_F16) return fail<H>(nullptr, CRTFX_E_INVALID, "unknown pixel format %d", pix_fmt);
     if (!fill) return fail<H>(nullptr, CRTFX_E_INVALID, "fill is null");
     const struct { const char* name; int v; } sizes[] = {{"src_h", src_h}, {"src_w", src_w}, {"win_h", win_h}, {"win_w", win_w}, {"dst_h", dst_h}, {"dst_w", dst_w}};
     for (const auto& s : sizes)
-        if (s.v < 1 || s.v > 32767) return fail<H>(nullptr, CRTFX_E_INVALID, "%s = %d outside 1..32767", s.name, s.v);
+        if (const int rc = crtfx_frames::check_size<H>(s.name, s.v)) return rc;
     if (win_y < 0 || win_y > src_h - win_h)
         return fail<H>(nullptr, CRTFX_E_INVALID, "win_y = %d: the window's rows %d..%d leave the source's %d", win_y, win_y, win_y + win_h, src_h);
     if (win_x < 0 || win_x > src_w - win_w)
@@ -256,85 +266,26 @@ int crtfx_canvas_create(int device, int pix_fmt, int src_h, int src_w, int win_y
     if (pix_fmt == CRTFX_PIX_U8)
         for (int c = 0; c < 3; ++c)
             if (fill[c] > 255) return fail<H>(nullptr, CRTFX_E_INVALID, "fill[%d] = %d outside 0..255 for uint8 frames", c, (int)fill[c]);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail<H>(nullptr, CRTFX_E_HIP, "no HIP device %d", device);
-    DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return fail<H>(nullptr, CRTFX_E_HIP, "hipSetDevice(%d): %s", device, hipGetErrorString(guard.err));
-    H* p = new (std::nothrow) H();
-    if (!p) return fail<H>(nullptr, CRTFX_E_NOMEM, "out of host memory");
-    p->device = device; p->bps = pix_fmt == CRTFX_PIX_F16 ? 2 : 1;
-    p->src_h = src_h; p->src_w = src_w; p->win_y = win_y; p->win_x = win_x; p->win_h = win_h; p->win_w = win_w;
-    p->dst_h = dst_h; p->dst_w = dst_w; p->dst_y = dst_y; p->dst_x = dst_x;
-    for (int c = 0; c < 3; ++c) p->fill[c] = fill[c];
-    p->src_bytes = (size_t)src_h * src_w * 3 * p->bps;
-    p->dst_bytes = (size_t)dst_h * dst_w * 3 * p->bps;
-    note_plan(p, vec_fits(p, nullptr, 0, 1), 0);
-    *out_plan = p;
-    return CRTFX_OK;
+    return crtfx_frames::new_plan<U>(device, out_plan, [&](H* p) {
+        p->src_bps = p->dst_bps = pix_fmt == CRTFX_PIX_F16 ? 2 : 1;
+        p->src_h = src_h; p->src_w = src_w; p->win_y = win_y; p->win_x = win_x; p->win_h = win_h; p->win_w = win_w;
+        p->dst_h = dst_h; p->dst_w = dst_w; p->dst_y = dst_y; p->dst_x = dst_x;
+        for (int c = 0; c < 3; ++c) p->fill[c] = fill[c];
+        p->src_bytes = (size_t)src_h * src_w * 3 * p->src_bps;
+        p->dst_bytes = (size_t)dst_h * dst_w * 3 * p->dst_bps;
+        return CRTFX_OK;
+    });
 }
 
-int crtfx_canvas_destroy(crtfx_canvas* p) {
-    if (!p) return CRTFX_OK;
-    DeviceGuard guard(p->device);
-    (void)hipDeviceSynchronize();
-    delete p;
-    return CRTFX_OK;
-}
+int crtfx_canvas_destroy(crtfx_canvas* p) { return crtfx_frames::destroy(p); }
 
-int crtfx_canvas_set_option(crtfx_canvas* p, int option, int value) {
-    if (!p) return CRTFX_E_INVALID;
-    if (option != CRTFX_CANVAS_OPT_FORCE_GENERAL) return fail(p, CRTFX_E_INVALID, "unknown canvas option %d", option);
-    if (value != 0 && value != 1) return fail(p, CRTFX_E_INVALID, "FORCE_GENERAL takes 0 or 1, got %d", value);
-    p->force_general = value != 0;
-    note_plan(p, vec_fits(p, nullptr, 0, 1), 0);
-    return CRTFX_OK;
-}
+int crtfx_canvas_set_option(crtfx_canvas* p, int option, int value) { return crtfx_frames::set_option<U>(p, option, value); }
 
-int crtfx_canvas_last_plan(crtfx_canvas* p, char* buf, size_t n) {
-    if (!p || !buf || n == 0) return CRTFX_E_INVALID;
-    snprintf(buf, n, "%s", p->plan);
-    return CRTFX_OK;
-}
+int crtfx_canvas_last_plan(crtfx_canvas* p, char* buf, size_t n) { return crtfx_frames::last_plan(p, buf, n); }
 
 int crtfx_canvas_run(crtfx_canvas* p, const void* src_base, size_t src_stride_bytes, void* dst_base, size_t dst_stride_bytes, int n, void* stream) {
-    if (!p) return CRTFX_E_INVALID;
-    if (n < 0) return fail(p, CRTFX_E_INVALID, "n = %d frames", n);
-    if (n == 0) { note_plan(p, vec_fits(p, dst_base, dst_stride_bytes, 0), 0); return CRTFX_OK; }
-    if (!src_base || !dst_base) return fail(p, CRTFX_E_INVALID, "null frame pointer");
-    const uintptr_t sb = reinterpret_cast<uintptr_t>(src_base), db = reinterpret_cast<uintptr_t>(dst_base);
-    if (p->bps == 2 && ((sb | db) & 1u || (n > 1 && ((src_stride_bytes | dst_stride_bytes) & 1u))))
-        return fail(p, CRTFX_E_INVALID, "half frames need even bases and strides");
-    if (n > 1 && (src_stride_bytes < p->src_bytes || dst_stride_bytes < p->dst_bytes))
-        return fail(p, CRTFX_E_INVALID, "frame strides %zu / %zu bytes are smaller than a frame (%zu / %zu)", src_stride_bytes, dst_stride_bytes, p->src_bytes, p->dst_bytes);
-    const uintptr_t se = sb + (size_t)(n - 1) * src_stride_bytes + p->src_bytes, de = db + (size_t)(n - 1) * dst_stride_bytes + p->dst_bytes;
-    if (sb < de && db < se) return fail(p, CRTFX_E_INVALID, "source and destination overlap");
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(p, CRTFX_E_HIP, "hipGetDevice failed");
-    if (dev != p->device) return fail(p, CRTFX_E_INVALID, "current device %d is not the plan's device %d (call hipSetDevice first)", dev, p->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool fits = vec_fits(p, dst_base, dst_stride_bytes, n);
-    Args a = make_args(p, fits);
-    a.src_stride = src_stride_bytes; a.dst_stride = dst_stride_bytes;
-    a.wide = !(db & 15u) && (n <= 1 || !(dst_stride_bytes & 15u));
-    const int group = 32768;                                           // grid.z
-    for (int f = 0; f < n; f += group) {
-        const unsigned g = n - f < group ? n - f : group;
-        a.src = static_cast<const uint8_t*>(src_base) + (size_t)f * src_stride_bytes;
-        a.dst = static_cast<uint8_t*>(dst_base) + (size_t)f * dst_stride_bytes;
-        if (fits) {
-            const dim3 grid((unsigned)((p->dst_bytes + 16u * BLOCK - 1) / (16u * BLOCK)), 1, g);
-            if (p->bps == 2) hipLaunchKernelGGL((k_canvas<f16, vec>), grid, dim3(BLOCK), 0, st, a);
-            else hipLaunchKernelGGL((k_canvas<u8, vec>), grid, dim3(BLOCK), 0, st, a);
-        } else {
-            const dim3 grid((a.dst_row + BLOCK - 1) / BLOCK, p->dst_h, g);
-            if (p->bps == 2) hipLaunchKernelGGL((k_canvas<f16, general>), grid, dim3(BLOCK), 0, st, a);
-            else hipLaunchKernelGGL((k_canvas<u8, general>), grid, dim3(BLOCK), 0, st, a);
-        }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(p, CRTFX_E_HIP, "canvas launch: %s", hipGetErrorString(e));
-    }
-    note_plan(p, fits, n);
-    return CRTFX_OK;
+    return crtfx_frames::run<U>(p, Batch{nullptr, src_base, src_stride_bytes, dst_base, dst_stride_bytes, n}, stream);
 }
 
 }  // extern "C"
+

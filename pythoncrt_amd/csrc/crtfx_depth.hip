@@ -8,7 +8,7 @@
 #include <type_traits>
 
 #include "crtfx_depth.h"
-#include "crtfx_stage_host.h"
+#include "crtfx_frame_host.h"
 
 namespace crtfx_depth_impl {
 
@@ -150,124 +150,47 @@ __global__ __launch_bounds__(BLOCK) void k_widen(Args a) {
 
 using namespace crtfx_depth_impl;
 
-struct crtfx_depth {
-    int device = 0;
+struct crtfx_depth : crtfx_frames::Plan {      // the side whose bps is 2 is the half side
     int h = 0, w = 0;
     bool narrow = false, dither = false;
     size_t samples = 0;                 // of one frame
-    size_t src_bytes = 0, dst_bytes = 0;
-    bool force_general = false;
-    char plan[128] = "";
-    std::string err;
 };
 
 namespace {
 
-using crtfx_stage::DeviceGuard;
+using crtfx_frames::Batch;
 using crtfx_stage::create_err;
 using crtfx_stage::fail;
 
-using H = crtfx_depth;
+struct U : crtfx_frames::Unit {
+    using H = crtfx_depth;
+    static constexpr int force_option = CRTFX_DEPTH_OPT_FORCE_GENERAL;
+    static constexpr const char* name = "depth";
 
-// the vec kernels' conditions (crtfx_depth.h)
-bool vec_fits(const H* p, const void* src, size_t src_stride, const void* dst, size_t dst_stride, int n) {
-    if (p->force_general) return false;
-    if (p->narrow ? (p->w & 7) != 0 : p->samples >= (1ull << 31)) return false;
-    if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 3u) return false;
-    return n <= 1 || !((src_stride | dst_stride) & 3u);
-}
+    // the vec kernels' conditions (crtfx_depth.h)
+    static bool vec_fits(const H* p, const Batch& b) {
+        if (p->force_general) return false;
+        if (p->narrow ? (p->w & 7) != 0 : p->samples >= (1ull << 31)) return false;
+        if ((reinterpret_cast<uintptr_t>(b.src) | reinterpret_cast<uintptr_t>(b.dst)) & 3u) return false;
+        return b.n <= 1 || !((b.src_stride | b.dst_stride) & 3u);
+    }
 
-void note_plan(H* p, bool vec, int frames) {
-    const char* path = vec ? "vec" : "general";
-    if (p->narrow) snprintf(p->plan, sizeof p->plan, "depth=k_narrow<%s,%s>;frames=%d", p->dither ? ordered::name : none::name, path, frames);
-    else snprintf(p->plan, sizeof p->plan, "depth=k_widen<%s>;frames=%d", path, frames);
-}
+    static void note_plan(H* p, bool vec, int frames) {
+        const char* path = vec ? "vec" : "general";
+        if (p->narrow) snprintf(p->plan, sizeof p->plan, "depth=k_narrow<%s,%s>;frames=%d", p->dither ? ordered::name : none::name, path, frames);
+        else snprintf(p->plan, sizeof p->plan, "depth=k_widen<%s>;frames=%d", path, frames);
+    }
 
-}  // namespace
+    static Args make_args(const H* p, bool fits, const Batch&) {
+        Args a{};
+        a.row = (uint32_t)p->w * 3u;
+        a.lanes_row = (uint32_t)p->w / 8u;
+        a.len = !fits ? 0u : p->narrow ? (uint32_t)p->h * a.lanes_row : (uint32_t)p->samples;
+        return a;
+    }
 
-extern "C" {
-
-const char* crtfx_depth_last_error(const crtfx_depth* p) { return p ? p->err.c_str() : create_err<H>().c_str(); }
-
-int crtfx_depth_create(int device, int h, int w, int direction, int dither, crtfx_depth** out_plan) {
-    create_err<H>().clear();
-    if (!out_plan) return fail<H>(nullptr, CRTFX_E_INVALID, "out_plan is null");
-    *out_plan = nullptr;
-    if (h < 1 || h > 32767) return fail<H>(nullptr, CRTFX_E_INVALID, "h = %d outside 1..32767", h);
-    if (w < 1 || w > 32767) return fail<H>(nullptr, CRTFX_E_INVALID, "w = %d outside 1..32767", w);
-    if (direction != CRTFX_DEPTH_WIDEN && direction != CRTFX_DEPTH_NARROW) return fail<H>(nullptr, CRTFX_E_INVALID, "unknown direction %d", direction);
-    if (dither != CRTFX_DITHER_NONE && dither != CRTFX_DITHER_ORDERED) return fail<H>(nullptr, CRTFX_E_INVALID, "unknown dither %d", dither);
-    if (direction == CRTFX_DEPTH_WIDEN && dither != CRTFX_DITHER_NONE)
-        return fail<H>(nullptr, CRTFX_E_INVALID, "dither = %d with direction = widen: widening is exact, there is nothing to dither", dither);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail<H>(nullptr, CRTFX_E_HIP, "no HIP device %d", device);
-    DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return fail<H>(nullptr, CRTFX_E_HIP, "hipSetDevice(%d): %s", device, hipGetErrorString(guard.err));
-    H* p = new (std::nothrow) H();
-    if (!p) return fail<H>(nullptr, CRTFX_E_NOMEM, "out of host memory");
-    p->device = device; p->h = h; p->w = w;
-    p->narrow = direction == CRTFX_DEPTH_NARROW; p->dither = dither == CRTFX_DITHER_ORDERED;
-    p->samples = (size_t)h * w * 3;
-    p->src_bytes = p->samples * (p->narrow ? 2 : 1);
-    p->dst_bytes = p->samples * (p->narrow ? 1 : 2);
-    note_plan(p, vec_fits(p, nullptr, 0, nullptr, 0, 1), 0);
-    *out_plan = p;
-    return CRTFX_OK;
-}
-
-int crtfx_depth_destroy(crtfx_depth* p) {
-    if (!p) return CRTFX_OK;
-    DeviceGuard guard(p->device);
-    (void)hipDeviceSynchronize();
-    delete p;
-    return CRTFX_OK;
-}
-
-int crtfx_depth_set_option(crtfx_depth* p, int option, int value) {
-    if (!p) return CRTFX_E_INVALID;
-    if (option != CRTFX_DEPTH_OPT_FORCE_GENERAL) return fail(p, CRTFX_E_INVALID, "unknown depth option %d", option);
-    if (value != 0 && value != 1) return fail(p, CRTFX_E_INVALID, "FORCE_GENERAL takes 0 or 1, got %d", value);
-    p->force_general = value != 0;
-    note_plan(p, vec_fits(p, nullptr, 0, nullptr, 0, 1), 0);
-    return CRTFX_OK;
-}
-
-int crtfx_depth_last_plan(crtfx_depth* p, char* buf, size_t n) {
-    if (!p || !buf || n == 0) return CRTFX_E_INVALID;
-    snprintf(buf, n, "%s", p->plan);
-    return CRTFX_OK;
-}
-
-int crtfx_depth_run(crtfx_depth* p, const void* src_base, size_t src_stride_bytes, void* dst_base, size_t dst_stride_bytes, int n, void* stream) {
-    if (!p) return CRTFX_E_INVALID;
-    if (n < 0) return fail(p, CRTFX_E_INVALID, "n = %d frames", n);
-    if (n == 0) { note_plan(p, vec_fits(p, src_base, src_stride_bytes, dst_base, dst_stride_bytes, 0), 0); return CRTFX_OK; }
-    if (!src_base || !dst_base) return fail(p, CRTFX_E_INVALID, "null frame pointer");
-    const uintptr_t sb = reinterpret_cast<uintptr_t>(src_base), db = reinterpret_cast<uintptr_t>(dst_base);
-    const uintptr_t half_base = p->narrow ? sb : db;
-    const size_t half_stride = p->narrow ? src_stride_bytes : dst_stride_bytes;
-    if ((half_base & 1u) || (n > 1 && (half_stride & 1u)))
-        return fail(p, CRTFX_E_INVALID, "half frames need even bases and strides");
-    if (n > 1 && (src_stride_bytes < p->src_bytes || dst_stride_bytes < p->dst_bytes))
-        return fail(p, CRTFX_E_INVALID, "frame strides %zu / %zu bytes are smaller than a frame (%zu / %zu)", src_stride_bytes, dst_stride_bytes, p->src_bytes, p->dst_bytes);
-    const uintptr_t se = sb + (size_t)(n - 1) * src_stride_bytes + p->src_bytes, de = db + (size_t)(n - 1) * dst_stride_bytes + p->dst_bytes;
-    if (sb < de && db < se) return fail(p, CRTFX_E_INVALID, "source and destination overlap");
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(p, CRTFX_E_HIP, "hipGetDevice failed");
-    if (dev != p->device) return fail(p, CRTFX_E_INVALID, "current device %d is not the plan's device %d (call hipSetDevice first)", dev, p->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool fits = vec_fits(p, src_base, src_stride_bytes, dst_base, dst_stride_bytes, n);
-    Args a{};
-    a.src_stride = src_stride_bytes; a.dst_stride = dst_stride_bytes;
-    a.row = (uint32_t)p->w * 3u;
-    a.lanes_row = (uint32_t)p->w / 8u;
-    a.len = !fits ? 0u : p->narrow ? (uint32_t)p->h * a.lanes_row : (uint32_t)p->samples;
-    const unsigned lanes = p->narrow ? a.len : (a.len + 15u) / 16u;     // vec: of one frame
-    const int group = 32768;                                            // grid.z
-    for (int f = 0; f < n; f += group) {
-        const unsigned g = n - f < group ? n - f : group;
-        a.src = static_cast<const uint8_t*>(src_base) + (size_t)f * src_stride_bytes;
-        a.dst = static_cast<uint8_t*>(dst_base) + (size_t)f * dst_stride_bytes;
+    static void launch(const H* p, bool fits, Args& a, int, unsigned g, hipStream_t st) {
+        const unsigned lanes = p->narrow ? a.len : (a.len + 15u) / 16u;     // vec: of one frame
         const dim3 grid = fits ? dim3((lanes + BLOCK - 1) / BLOCK, 1, g) : dim3((a.row + BLOCK - 1) / BLOCK, p->h, g);
         if (!p->narrow) {
             if (fits) hipLaunchKernelGGL((k_widen<vec>), grid, dim3(BLOCK), 0, st, a);
@@ -279,11 +202,44 @@ int crtfx_depth_run(crtfx_depth* p, const void* src_base, size_t src_stride_byte
             if (fits) hipLaunchKernelGGL((k_narrow<none, vec>), grid, dim3(BLOCK), 0, st, a);
             else hipLaunchKernelGGL((k_narrow<none, general>), grid, dim3(BLOCK), 0, st, a);
         }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(p, CRTFX_E_HIP, "depth launch: %s", hipGetErrorString(e));
     }
-    note_plan(p, fits, n);
-    return CRTFX_OK;
+};
+
+}  // namespace
+
+extern "C" {
+
+const char* crtfx_depth_last_error(const crtfx_depth* p) { return p ? p->err.c_str() : create_err<crtfx_depth>().c_str(); }
+
+int crtfx_depth_create(int device, int h, int w, int direction, int dither, crtfx_depth** out_plan) {
+    using H = crtfx_depth;
+    if (const int rc = crtfx_frames::begin_create(out_plan)) return rc;
+    if (const int rc = crtfx_frames::check_size<H>("h", h)) return rc;
+    if (const int rc = crtfx_frames::check_size<H>("w", w)) return rc;
+    if (direction != CRTFX_DEPTH_WIDEN && direction != CRTFX_DEPTH_NARROW) return fail<H>(nullptr, CRTFX_E_INVALID, "unknown direction %d", direction);
+    if (dither != CRTFX_DITHER_NONE && dither != CRTFX_DITHER_ORDERED) return fail<H>(nullptr, CRTFX_E_INVALID, "unknown dither %d", dither);
+    if (direction == CRTFX_DEPTH_WIDEN && dither != CRTFX_DITHER_NONE)
+        return fail<H>(nullptr, CRTFX_E_INVALID, "dither = %d with direction = widen: widening is exact, there is nothing to dither", dither);
+    return crtfx_frames::new_plan<U>(device, out_plan, [&](H* p) {
+        p->h = h; p->w = w;
+        p->narrow = direction == CRTFX_DEPTH_NARROW; p->dither = dither == CRTFX_DITHER_ORDERED;
+        p->samples = (size_t)h * w * 3;
+        p->src_bps = p->narrow ? 2 : 1; p->dst_bps = p->narrow ? 1 : 2;
+        p->src_bytes = p->samples * p->src_bps;
+        p->dst_bytes = p->samples * p->dst_bps;
+        return CRTFX_OK;
+    });
+}
+
+int crtfx_depth_destroy(crtfx_depth* p) { return crtfx_frames::destroy(p); }
+
+int crtfx_depth_set_option(crtfx_depth* p, int option, int value) { return crtfx_frames::set_option<U>(p, option, value); }
+
+int crtfx_depth_last_plan(crtfx_depth* p, char* buf, size_t n) { return crtfx_frames::last_plan(p, buf, n); }
+
+int crtfx_depth_run(crtfx_depth* p, const void* src_base, size_t src_stride_bytes, void* dst_base, size_t dst_stride_bytes, int n, void* stream) {
+    return crtfx_frames::run<U>(p, Batch{nullptr, src_base, src_stride_bytes, dst_base, dst_stride_bytes, n}, stream);
 }
 
 }  // extern "C"
+

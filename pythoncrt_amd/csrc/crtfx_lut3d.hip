@@ -9,7 +9,7 @@
 #include <vector>
 
 #include "crtfx_lut3d.h"
-#include "crtfx_stage_host.h"
+#include "crtfx_frame_host.h"
 
 namespace crtfx_lut3d_impl {
 
@@ -199,22 +199,21 @@ __global__ __launch_bounds__(BLOCK) void k_lut3d(Args a) {
 
 using namespace crtfx_lut3d_impl;
 
-struct crtfx_lut3d {
-    int device = 0;
+struct crtfx_lut3d : crtfx_frames::Plan {      // one frame size and sample type on both sides
     int h = 0, w = 0, N = 0;
     bool half = false;
     uint32_t cube = 0;                  // N^3
     size_t lds_bytes = 0;               // 4 * N^3 rounded up to 16; 0 where the cube does not fit a CU's LDS
-    size_t pixels = 0, frame_bytes = 0;
+    size_t pixels = 0;
     uint32_t* table = nullptr;          // device: the packed cube
     int cus = 0;
-    bool force_general = false, force_global = false;
-    char plan[160] = "";
-    std::string err;
+    bool force_global = false;
+    ~crtfx_lut3d() { if (table) (void)hipFree(table); }
 };
 
 namespace {
 
+using crtfx_frames::Batch;
 using crtfx_stage::DeviceGuard;
 using crtfx_stage::create_err;
 using crtfx_stage::fail;
@@ -225,19 +224,6 @@ using H = crtfx_lut3d;
 bool lds_default(int N) { return N <= CRTFX_LUT3D_LDS_MAX_N; }
 
 bool use_lds(const H* p) { return !p->force_global && lds_default(p->N); }
-
-// the vec walk's conditions (crtfx_lut3d.h)
-bool vec_fits(const H* p, const void* src, size_t src_stride, const void* dst, size_t dst_stride, int n) {
-    if (p->force_general) return false;
-    if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 3u) return false;
-    return n <= 1 || !((src_stride | dst_stride) & 3u);
-}
-
-void note_plan(H* p, bool vec_path, int frames) {
-    const bool l = use_lds(p);
-    snprintf(p->plan, sizeof p->plan, "lut3d=k_lut3d<%s,%s,%s>;n=%d;lds=%zu;frames=%d", p->half ? half::name : u8::name, l ? lds::name : global::name,
-             vec_path ? vec::name : general::name, p->N, l ? (size_t)p->cube * 4u : (size_t)0, frames);
-}
 
 // -1, or the index of the first entry above 1020
 long long bad_entry(int N, const uint16_t* table) {
@@ -270,7 +256,7 @@ void launch_walk(bool vec_path, dim3 grid, size_t shmem, hipStream_t st, const A
 }
 
 template <class T>
-void launch(bool in_lds, bool vec_path, dim3 grid, size_t shmem, hipStream_t st, const Args& a) {
+void launch_table(bool in_lds, bool vec_path, dim3 grid, size_t shmem, hipStream_t st, const Args& a) {
     if (in_lds) launch_walk<T, lds>(vec_path, grid, shmem, st, a);
     else launch_walk<T, global>(vec_path, grid, 0, st, a);
 }
@@ -285,6 +271,54 @@ hipError_t raise_lds_limit() {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lut3d<T, lds, general>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
+// the table of a new plan, with the plan's device current
+hipError_t upload(H* p, const std::vector<uint32_t>& packed) {
+    hipError_t e = hipDeviceGetAttribute(&p->cus, hipDeviceAttributeMultiprocessorCount, p->device);
+    if (e == hipSuccess && p->cus < 1) p->cus = 1;
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->table), packed.size() * 4);
+    if (e == hipSuccess) e = hipMemcpy(p->table, packed.data(), packed.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && p->lds_bytes > 65536) e = p->half ? raise_lds_limit<half>() : raise_lds_limit<u8>();
+    return e;
+}
+
+struct U : crtfx_frames::Unit {
+    using H = crtfx_lut3d;
+    static constexpr const char* name = "lut3d";
+    static constexpr bool one_size = true;
+
+    // the vec walk's conditions (crtfx_lut3d.h)
+    static bool vec_fits(const H* p, const Batch& b) {
+        if (p->force_general) return false;
+        if ((reinterpret_cast<uintptr_t>(b.src) | reinterpret_cast<uintptr_t>(b.dst)) & 3u) return false;
+        return b.n <= 1 || !((b.src_stride | b.dst_stride) & 3u);
+    }
+
+    static void note_plan(H* p, bool vec_path, int frames) {
+        const bool l = use_lds(p);
+        snprintf(p->plan, sizeof p->plan, "lut3d=k_lut3d<%s,%s,%s>;n=%d;lds=%zu;frames=%d", p->half ? half::name : u8::name, l ? lds::name : global::name,
+                 vec_path ? vec::name : general::name, p->N, l ? (size_t)p->cube * 4u : (size_t)0, frames);
+    }
+
+    static Args make_args(const H* p, bool fits, const Batch&) {
+        Args a{};
+        a.table = p->table; a.cube = p->cube; a.N = (uint32_t)p->N;
+        a.pixels = (uint32_t)p->pixels;                                 // 32767^2 < 2^30
+        a.items = fits ? (a.pixels + 3u) / 4u : a.pixels;
+        return a;
+    }
+
+    static int group(const Args& a) { return (int)(0x7fffffffu / a.items); }       // frames of one launch: frames * items < 2^31
+
+    static void launch(const H* p, bool fits, Args& a, int, unsigned g, hipStream_t st) {
+        const bool in_lds = use_lds(p);
+        const unsigned per_cu = in_lds ? (CRTFX_LUT3D_LDS_BYTES / p->lds_bytes < 2 ? 1u : 2u) : 2u;        // blocks of 1024 lanes: two fill a CU
+        a.frames = g;
+        const unsigned need = (a.frames * a.items + BLOCK - 1) / BLOCK, most = (unsigned)p->cus * per_cu;
+        const dim3 grid(need < most ? need : most);
+        if (p->half) launch_table<half>(in_lds, fits, grid, p->lds_bytes, st, a); else launch_table<u8>(in_lds, fits, grid, p->lds_bytes, st, a);
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -292,50 +326,27 @@ extern "C" {
 const char* crtfx_lut3d_last_error(const crtfx_lut3d* p) { return p ? p->err.c_str() : create_err<H>().c_str(); }
 
 int crtfx_lut3d_create(int device, int h, int w, int pix_fmt, int N, const uint16_t* table, crtfx_lut3d** out_plan) {
-    create_err<H>().clear();
-    if (!out_plan) return fail<H>(nullptr, CRTFX_E_INVALID, "out_plan is null");
-    *out_plan = nullptr;
+    if (const int rc = crtfx_frames::begin_create(out_plan)) return rc;
     if (pix_fmt != CRTFX_PIX_U8 && pix_fmt != CRTFX_PIX_F16) return fail<H>(nullptr, CRTFX_E_INVALID, "unknown pix_fmt %d", pix_fmt);
-    if (h < 1 || h > 32767) return fail<H>(nullptr, CRTFX_E_INVALID, "h = %d outside 1..32767", h);
-    if (w < 1 || w > 32767) return fail<H>(nullptr, CRTFX_E_INVALID, "w = %d outside 1..32767", w);
+    if (const int rc = crtfx_frames::check_size<H>("h", h)) return rc;
+    if (const int rc = crtfx_frames::check_size<H>("w", w)) return rc;
     if (N < CRTFX_LUT3D_MIN_N || N > CRTFX_LUT3D_MAX_N) return fail<H>(nullptr, CRTFX_E_INVALID, "N = %d outside %d..%d", N, CRTFX_LUT3D_MIN_N, CRTFX_LUT3D_MAX_N);
     if (const int rc = check_table<H>(nullptr, N, table)) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail<H>(nullptr, CRTFX_E_HIP, "no HIP device %d", device);
-    DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return fail<H>(nullptr, CRTFX_E_HIP, "hipSetDevice(%d): %s", device, hipGetErrorString(guard.err));
-    H* p = new (std::nothrow) H();
-    if (!p) return fail<H>(nullptr, CRTFX_E_NOMEM, "out of host memory");
-    p->device = device; p->h = h; p->w = w; p->N = N; p->half = pix_fmt == CRTFX_PIX_F16;
-    p->cube = (uint32_t)N * N * N;
-    p->pixels = (size_t)h * w;
-    p->frame_bytes = p->pixels * 3 * (p->half ? 2 : 1);
-    const std::vector<uint32_t> packed = pack(N, table);
-    p->lds_bytes = N <= CRTFX_LUT3D_LDS_MAX_N ? packed.size() * 4 : 0;
-    hipError_t e = hipDeviceGetAttribute(&p->cus, hipDeviceAttributeMultiprocessorCount, device);
-    if (e == hipSuccess && p->cus < 1) p->cus = 1;
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->table), packed.size() * 4);
-    if (e == hipSuccess) e = hipMemcpy(p->table, packed.data(), packed.size() * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && p->lds_bytes > 65536) e = p->half ? raise_lds_limit<half>() : raise_lds_limit<u8>();
-    if (e != hipSuccess) {
-        const int rc = fail<H>(nullptr, e == hipErrorOutOfMemory ? CRTFX_E_NOMEM : CRTFX_E_HIP, "lut3d create: %s", hipGetErrorString(e));
-        if (p->table) (void)hipFree(p->table);
-        delete p;
-        return rc;
-    }
-    note_plan(p, vec_fits(p, nullptr, 0, nullptr, 0, 1), 0);
-    *out_plan = p;
-    return CRTFX_OK;
+    return crtfx_frames::new_plan<U>(device, out_plan, [&](H* p) -> int {
+        p->h = h; p->w = w; p->N = N; p->half = pix_fmt == CRTFX_PIX_F16;
+        p->cube = (uint32_t)N * N * N;
+        p->pixels = (size_t)h * w;
+        p->src_bps = p->dst_bps = p->half ? 2 : 1;
+        p->src_bytes = p->dst_bytes = p->pixels * 3 * p->src_bps;
+        const std::vector<uint32_t> packed = pack(N, table);
+        p->lds_bytes = lds_default(N) ? packed.size() * 4 : 0;
+        const hipError_t e = upload(p, packed);
+        if (e != hipSuccess) return fail<H>(nullptr, e == hipErrorOutOfMemory ? CRTFX_E_NOMEM : CRTFX_E_HIP, "lut3d create: %s", hipGetErrorString(e));
+        return CRTFX_OK;
+    });
 }
 
-int crtfx_lut3d_destroy(crtfx_lut3d* p) {
-    if (!p) return CRTFX_OK;
-    DeviceGuard guard(p->device);
-    (void)hipDeviceSynchronize();
-    if (p->table) (void)hipFree(p->table);
-    delete p;
-    return CRTFX_OK;
-}
+int crtfx_lut3d_destroy(crtfx_lut3d* p) { return crtfx_frames::destroy(p); }
 
 int crtfx_lut3d_set_table(crtfx_lut3d* p, int N, const uint16_t* table) {
     if (!p) return CRTFX_E_INVALID;
@@ -350,58 +361,22 @@ int crtfx_lut3d_set_table(crtfx_lut3d* p, int N, const uint16_t* table) {
     return CRTFX_OK;
 }
 
+// two options: an entry point of its own
 int crtfx_lut3d_set_option(crtfx_lut3d* p, int option, int value) {
     if (!p) return CRTFX_E_INVALID;
     if (option != CRTFX_LUT3D_OPT_FORCE_GENERAL && option != CRTFX_LUT3D_OPT_FORCE_GLOBAL) return fail(p, CRTFX_E_INVALID, "unknown lut3d option %d", option);
     const char* name = option == CRTFX_LUT3D_OPT_FORCE_GENERAL ? "FORCE_GENERAL" : "FORCE_GLOBAL";
     if (value != 0 && value != 1) return fail(p, CRTFX_E_INVALID, "%s takes 0 or 1, got %d", name, value);
     if (option == CRTFX_LUT3D_OPT_FORCE_GENERAL) p->force_general = value != 0; else p->force_global = value != 0;
-    note_plan(p, vec_fits(p, nullptr, 0, nullptr, 0, 1), 0);
+    U::note_plan(p, U::vec_fits(p, Batch{nullptr, nullptr, 0, nullptr, 0, 1}), 0);
     return CRTFX_OK;
 }
 
-int crtfx_lut3d_last_plan(crtfx_lut3d* p, char* buf, size_t n) {
-    if (!p || !buf || n == 0) return CRTFX_E_INVALID;
-    snprintf(buf, n, "%s", p->plan);
-    return CRTFX_OK;
-}
+int crtfx_lut3d_last_plan(crtfx_lut3d* p, char* buf, size_t n) { return crtfx_frames::last_plan(p, buf, n); }
 
 int crtfx_lut3d_run(crtfx_lut3d* p, const void* src_base, size_t src_stride_bytes, void* dst_base, size_t dst_stride_bytes, int n, void* stream) {
-    if (!p) return CRTFX_E_INVALID;
-    if (n < 0) return fail(p, CRTFX_E_INVALID, "n = %d frames", n);
-    if (n == 0) { note_plan(p, vec_fits(p, src_base, src_stride_bytes, dst_base, dst_stride_bytes, 0), 0); return CRTFX_OK; }
-    if (!src_base || !dst_base) return fail(p, CRTFX_E_INVALID, "null frame pointer");
-    const uintptr_t sb = reinterpret_cast<uintptr_t>(src_base), db = reinterpret_cast<uintptr_t>(dst_base);
-    if (p->half && (((sb | db) & 1u) || (n > 1 && ((src_stride_bytes | dst_stride_bytes) & 1u))))
-        return fail(p, CRTFX_E_INVALID, "half frames need even bases and strides");
-    if (n > 1 && (src_stride_bytes < p->frame_bytes || dst_stride_bytes < p->frame_bytes))
-        return fail(p, CRTFX_E_INVALID, "frame strides %zu / %zu bytes are smaller than a frame (%zu)", src_stride_bytes, dst_stride_bytes, p->frame_bytes);
-    const uintptr_t se = sb + (size_t)(n - 1) * src_stride_bytes + p->frame_bytes, de = db + (size_t)(n - 1) * dst_stride_bytes + p->frame_bytes;
-    if (sb < de && db < se) return fail(p, CRTFX_E_INVALID, "source and destination overlap");
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(p, CRTFX_E_HIP, "hipGetDevice failed");
-    if (dev != p->device) return fail(p, CRTFX_E_INVALID, "current device %d is not the plan's device %d (call hipSetDevice first)", dev, p->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool fits = vec_fits(p, src_base, src_stride_bytes, dst_base, dst_stride_bytes, n), in_lds = use_lds(p);
-    Args a{};
-    a.src_stride = src_stride_bytes; a.dst_stride = dst_stride_bytes;
-    a.table = p->table; a.cube = p->cube; a.N = (uint32_t)p->N;
-    a.pixels = (uint32_t)p->pixels;                                     // 32767^2 < 2^30
-    a.items = fits ? (a.pixels + 3u) / 4u : a.pixels;
-    const unsigned per_cu = in_lds ? (CRTFX_LUT3D_LDS_BYTES / p->lds_bytes < 2 ? 1u : 2u) : 2u;        // blocks of 1024 lanes: two fill a CU
-    const int group = (int)(0x7fffffffu / a.items);                     // frames of one launch: frames * items < 2^31
-    for (int f = 0; f < n; f += group) {
-        a.frames = (uint32_t)(n - f < group ? n - f : group);
-        a.src = static_cast<const uint8_t*>(src_base) + (size_t)f * src_stride_bytes;
-        a.dst = static_cast<uint8_t*>(dst_base) + (size_t)f * dst_stride_bytes;
-        const unsigned need = (a.frames * a.items + BLOCK - 1) / BLOCK, most = (unsigned)p->cus * per_cu;
-        const dim3 grid(need < most ? need : most);
-        if (p->half) launch<half>(in_lds, fits, grid, p->lds_bytes, st, a); else launch<u8>(in_lds, fits, grid, p->lds_bytes, st, a);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(p, CRTFX_E_HIP, "lut3d launch: %s", hipGetErrorString(e));
-    }
-    note_plan(p, fits, n);
-    return CRTFX_OK;
+    return crtfx_frames::run<U>(p, Batch{nullptr, src_base, src_stride_bytes, dst_base, dst_stride_bytes, n}, stream);
 }
 
 }  // extern "C"
+

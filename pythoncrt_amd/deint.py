@@ -8,14 +8,14 @@ from __future__ import annotations
 from typing import Tuple
 
 from . import _lib
-from ._stage import Handle
+from ._stage import FramePlan, pix_format
 
 METHODS = ("linear", "edge")
 ORDERS = ("tff", "bff")
 FIELDS = ("first", "both")
 
 
-class Deinterlace(Handle):
+class Deinterlace(FramePlan):
     """plan = Deinterlace(device, (h, w), method="linear", order="tff", fields="first", dtype=None);
     out = plan.run(frames[n, h, w, 3]) -> [n * frames_out, h, w, 3] of the same dtype (plan(frames) is the same call): source frame i
     gives output frame i ("first") or output frames 2 i and 2 i + 1 ("both").  `dtype` is torch.uint8 (default) or torch.float16.
@@ -33,27 +33,10 @@ class Deinterlace(Handle):
         self.method, self.order, self.fields = method, order, fields
         self.frames_out = 2 if fields == "both" else 1
         self._open(device)
-        import torch
-        self.dtype = torch.uint8 if dtype is None else dtype
-        if self.dtype not in (torch.uint8, torch.float16):
-            raise ValueError(f"dtype must be torch.uint8 or torch.float16, got {dtype!r}")
+        self.dtype, pix_fmt = pix_format(dtype)
         self.size = (int(size[0]), int(size[1]))
-        self._create(self.size[0], self.size[1], _lib.PIX_F16 if self.dtype == torch.float16 else _lib.PIX_U8, METHODS.index(method),
-                     ORDERS.index(order), FIELDS.index(fields))
+        self._create(self.size[0], self.size[1], pix_fmt, METHODS.index(method), ORDERS.index(order), FIELDS.index(fields))
         assert self._fn("frames_out")(self._plan) == self.frames_out
+        self._frames(self.size + (self.dtype,))
         if force_general:
             self.force_general = True
-
-    def run(self, frames, out=None):
-        import torch
-        h, w = self.size
-        if frames.dtype != self.dtype:
-            raise _lib.CrtfxError(_lib.E_UNSUPPORTED, f"this plan takes {self.dtype} RGB frames, got {frames.dtype}")
-        if frames.dim() != 4 or tuple(frames.shape[1:]) != (h, w, 3) or frames.device != self.device:
-            raise ValueError(f"frames must be {self.dtype} [n, {h}, {w}, 3] on {self.device}, got {tuple(frames.shape)} on {frames.device}")
-        n = int(frames.shape[0])
-        if out is None:
-            out = torch.empty((n * self.frames_out, h, w, 3), dtype=self.dtype, device=self.device)
-        if out.dtype != self.dtype or tuple(out.shape) != (n * self.frames_out, h, w, 3) or out.device != self.device:
-            raise ValueError(f"out must be {self.dtype} [{n * self.frames_out}, {h}, {w}, 3] on {self.device}")
-        return self._run(frames, out, n)

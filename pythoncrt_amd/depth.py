@@ -7,7 +7,7 @@ from __future__ import annotations
 from typing import Tuple
 
 from . import _lib
-from ._stage import Handle
+from ._stage import FramePlan
 
 DITHERS = ("none", "ordered")
 
@@ -22,7 +22,7 @@ BAYER8 = ((0, 32, 8, 40, 2, 34, 10, 42),
           (63, 31, 55, 23, 61, 29, 53, 21))
 
 
-class _Depth(Handle):
+class _Depth(FramePlan):
     """What the two directions share: out = plan.run(frames[n, h, w, 3] of `_src`) -> [n, h, w, 3] of `_dst` (plan(frames) is the same
     call).  `frames` and `out` are tensors on `device` whose frames are contiguous (the batch stride is free: slices of larger tensors are
     fine).  The work is enqueued on the current stream of `device`; nothing synchronises."""
@@ -32,26 +32,13 @@ class _Depth(Handle):
     _src, _dst = "uint8", "float16"
 
     def _plan_for(self, device, size, dither, force_general):
+        import torch
         self._open(device)
         self.size = (int(size[0]), int(size[1]))
         self._create(self.size[0], self.size[1], self._direction, dither)
+        self._frames(self.size + (getattr(torch, self._src),), self.size + (getattr(torch, self._dst),))
         if force_general:
             self.force_general = True
-
-    def run(self, frames, out=None):
-        import torch
-        h, w = self.size
-        src, dst = getattr(torch, self._src), getattr(torch, self._dst)
-        if frames.dtype != src:
-            raise _lib.CrtfxError(_lib.E_UNSUPPORTED, f"this plan takes {self._src} RGB frames, got {frames.dtype}")
-        if frames.dim() != 4 or tuple(frames.shape[1:]) != (h, w, 3) or frames.device != self.device:
-            raise ValueError(f"frames must be {self._src} [n, {h}, {w}, 3] on {self.device}, got {tuple(frames.shape)} on {frames.device}")
-        n = int(frames.shape[0])
-        if out is None:
-            out = torch.empty((n, h, w, 3), dtype=dst, device=self.device)
-        if out.dtype != dst or tuple(out.shape) != (n, h, w, 3) or out.device != self.device:
-            raise ValueError(f"out must be {self._dst} [{n}, {h}, {w}, 3] on {self.device}")
-        return self._run(frames, out, n)
 
 
 class Widen(_Depth):

@@ -10,11 +10,11 @@ from typing import Tuple
 import numpy as np
 
 from . import _lib
-from ._stage import Handle
+from ._stage import FramePlan, pix_format
 from .cube import Cube, as_cube
 
 
-class Lut3D(Handle):
+class Lut3D(FramePlan):
     """plan = Lut3D(device, (h, w), cube, dtype=torch.uint8); out = plan.run(frames[n, h, w, 3]) -> the same dtype and shape (plan(frames)
     is the same call).  `frames` and `out` are tensors on `device` whose frames are contiguous (the batch stride is free: slices of larger
     tensors are fine) and do not overlap.  The work is enqueued on the current stream of `device`; only creating the plan and set_cube
@@ -24,17 +24,13 @@ class Lut3D(Handle):
     _force_option = _lib.LUT3D_OPT_FORCE_GENERAL
 
     def __init__(self, device, size: Tuple[int, int], cube, dtype=None, force_general: bool = False):
-        import torch
-        dtype = torch.uint8 if dtype is None else dtype
-        if dtype not in (torch.uint8, torch.float16):
-            raise ValueError(f"dtype must be torch.uint8 or torch.float16, got {dtype}")
-        cube = as_cube(cube)
+        self.dtype, pix_fmt = pix_format(dtype)
+        self.cube = cube = as_cube(cube)
         self._open(device)
         self.size = (int(size[0]), int(size[1]))
-        self.dtype, self.cube = dtype, cube
         table = self._table(cube)
-        self._create(self.size[0], self.size[1], _lib.PIX_F16 if dtype == torch.float16 else _lib.PIX_U8, cube.size,
-                     table.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)))
+        self._create(self.size[0], self.size[1], pix_fmt, cube.size, table.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)))
+        self._frames(self.size + (self.dtype,))
         self._force_global = False
         if force_general:
             self.force_general = True
@@ -61,17 +57,3 @@ class Lut3D(Handle):
     def force_global(self, value) -> None:
         self.set_option(_lib.LUT3D_OPT_FORCE_GLOBAL, 1 if value else 0)
         self._force_global = bool(value)
-
-    def run(self, frames, out=None):
-        import torch
-        h, w = self.size
-        if frames.dtype != self.dtype:
-            raise _lib.CrtfxError(_lib.E_UNSUPPORTED, f"this plan takes {self.dtype} RGB frames, got {frames.dtype}")
-        if frames.dim() != 4 or tuple(frames.shape[1:]) != (h, w, 3) or frames.device != self.device:
-            raise ValueError(f"frames must be {self.dtype} [n, {h}, {w}, 3] on {self.device}, got {tuple(frames.shape)} on {frames.device}")
-        n = int(frames.shape[0])
-        if out is None:
-            out = torch.empty((n, h, w, 3), dtype=self.dtype, device=self.device)
-        if out.dtype != self.dtype or tuple(out.shape) != (n, h, w, 3) or out.device != self.device:
-            raise ValueError(f"out must be {self.dtype} [{n}, {h}, {w}, 3] on {self.device}")
-        return self._run(frames, out, n)

@@ -1,5 +1,6 @@
 """The one format registry (pythoncrt_amd/formats.py) against the CLI's flags and the family modules, and the generated ctypes tables of the
-format stages (_lib.stage_symbols) against the seven entry points written out.  No GPU."""
+format stages (_lib.stage_symbols) against the seven entry points written out; the same for the resize stages (_lib.resize_symbols) and the
+frame stages (_lib.frame_symbols).  No GPU."""
 import argparse
 import ctypes
 
@@ -136,3 +137,59 @@ def test_the_tall_case_of_the_resize_api_test_passes_the_table_checks(family, pi
                                                 tables.ptr(ay[0]), tables.ptr(ay[1]), tables.ptr(ay[2]), ay[2].shape[1], ctypes.byref(plan))
     msg = (getattr(lib, f"crtfx_{family}_last_error")(None) or b"").decode()
     assert rc == _lib.E_HIP and not plan.value and msg == "no HIP device 4096", (rc, msg)
+
+
+_FRAME_OWN = {        # family -> (create's own arguments behind `device`, the entry points beside the shared five)
+    "canvas": ([ctypes.c_int] * 11 + [ctypes.POINTER(ctypes.c_uint16)], {}),
+    "depth": ([ctypes.c_int] * 4, {}),
+    "deint": ([ctypes.c_int] * 6, {"frames_out": (ctypes.c_int, [ctypes.c_void_p])}),
+    "adeint": ([ctypes.c_int] * 5, {"frames_out": (ctypes.c_int, [ctypes.c_void_p]),
+                                    "run": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int,
+                                                           ctypes.c_void_p])}),
+    "lut3d": ([ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_uint16)],
+              {"set_table": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_uint16)])}),
+}
+
+
+def _literal_frame(fam):
+    vp = ctypes.c_void_p
+    create_args, extra = _FRAME_OWN[fam]
+    table = {
+        f"crtfx_{fam}_create": (ctypes.c_int, [ctypes.c_int] + create_args + [ctypes.POINTER(vp)]),
+        f"crtfx_{fam}_destroy": (ctypes.c_int, [vp]),
+        f"crtfx_{fam}_last_error": (ctypes.c_char_p, [vp]),
+        f"crtfx_{fam}_run": (ctypes.c_int, [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_int, vp]),
+        f"crtfx_{fam}_set_option": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
+        f"crtfx_{fam}_last_plan": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t]),
+    }
+    for name, sig in extra.items():                                            # a further entry point goes behind the six; the family's own run stays in run's place
+        table[f"crtfx_{fam}_{name}"] = sig
+    return table
+
+
+@pytest.mark.parametrize("table,family,classes,option", [("CANVAS_SYMBOLS", "canvas", ("Canvas",), "CANVAS_OPT_FORCE_GENERAL"),
+                                                         ("DEPTH_SYMBOLS", "depth", ("Widen", "Narrow"), "DEPTH_OPT_FORCE_GENERAL"),
+                                                         ("DEINT_SYMBOLS", "deint", ("Deinterlace",), "DEINT_OPT_FORCE_GENERAL"),
+                                                         ("ADEINT_SYMBOLS", "adeint", ("AdaptiveDeinterlace",), "ADEINT_OPT_FORCE_GENERAL"),
+                                                         ("LUT3D_SYMBOLS", "lut3d", ("Lut3D",), "LUT3D_OPT_FORCE_GENERAL")])
+def test_generated_frame_symbol_tables_equal_the_literal(table, family, classes, option):
+    """_lib.frame_symbols against the entry points of a frame stage written out, contents and order (the SIGNATURES of the five
+    test_*_tables.py files are the same tables, each beside its header); _lib.load() binds them; the plan classes stand on FramePlan and on
+    neither of the other two bases, call exactly this family, and their force option is the family's *_OPT_FORCE_GENERAL."""
+    import pythoncrt_amd as pc
+    from pythoncrt_amd import _stage
+    create_args, extra = _FRAME_OWN[family]
+    want = _literal_frame(family)
+    got = getattr(_lib, table)
+    assert got == want and len(got) == 6 + len([k for k in extra if k != "run"]) and list(got) == list(want)
+    assert got == _lib.frame_symbols(family, create_args, **extra) and list(got) == list(_lib.frame_symbols(family, create_args, **extra))
+    lib = _lib.load()
+    for name, (res, args) in want.items():
+        assert getattr(lib, name).restype == res and getattr(lib, name).argtypes == args, name
+    for cls in classes:
+        plan = getattr(pc, cls)
+        assert issubclass(plan, _stage.FramePlan) and issubclass(plan, _stage.Handle)
+        assert not issubclass(plan, _stage.StagePlan) and not issubclass(plan, _stage.ResizePlan)
+        assert plan._family == family and plan._force_option == 1 == getattr(_lib, option)
+    names = [s.rsplit("/", 1)[-1] for s in _lib.SOURCES]                     # the rebuild check reads the skeleton
+    assert "crtfx_frame_host.h" in names and f"crtfx_{family}.hip" in names
