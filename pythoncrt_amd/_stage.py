@@ -2,7 +2,7 @@
 create and its error path, options, the batched run, the plan string, close.  On it stand `StagePlan` — the ten format-stage plans
 (unpack.py, egress.py, deep.py, yuv422.py, deep444.py) and the two sited plans (sited.py: source and egress), seven entry points each
 (`_lib.stage_symbols`) — `ResizePlan` — the three resize plans (ingest.py, resize16.py, resample.py), six entry points each
-(`_lib.resize_symbols`) — and `FramePlan` — the six plans of the five frame stages (canvas.py, depth.py, deint.py, adeint.py, lut3d.py), six
+(`_lib.resize_symbols`) — and `FramePlan` — the seven plans of the six frame stages (canvas.py, depth.py, deint.py, adeint.py, lut3d.py, interlace.py), six
 entry points and a create of its own each (`_lib.frame_symbols`).  A family module declares short classes on `SourcePlan` / `EgressPlan` /
 `ResizePlan` / `FramePlan` — family name, C layout numbers or dtype, table function, frame size, its own arguments — and keeps what is truly
 its own; everything else is here."""
@@ -217,9 +217,10 @@ def pix_format(dtype, error=ValueError):
 
 
 class FramePlan(Handle):
-    """A frame stage: out = plan.run(frames[n, sh, sw, 3]) -> [n * frames_out, dh, dw, 3], either side of a dtype of its own (plan(frames)
-    is the same call).  A plan says what it takes and gives with `_frames` before it is run."""
-    frames_out = 1               # output frames per source frame
+    """A frame stage: out = plan.run(frames[n, sh, sw, 3]) -> [ceil(n / frames_in) * frames_out, dh, dw, 3], either side of a dtype of its
+    own (plan(frames) is the same call).  A plan says what it takes and gives with `_frames` before it is run."""
+    frames_out = 1               # output frames per ...
+    frames_in = 1                # ... this many source frames
 
     def _frames(self, takes, gives=None):
         """(h, w, torch dtype) of one source frame and of one output frame (the same unless given)."""
@@ -237,7 +238,7 @@ class FramePlan(Handle):
     def _check_out(self, n, out):
         import torch
         h, w, dtype = self._gives
-        shape = (n * self.frames_out, h, w, 3)
+        shape = (-(-n // self.frames_in) * self.frames_out, h, w, 3)
         if out is None:
             return torch.empty(shape, dtype=dtype, device=self.device)
         if out.dtype != dtype or tuple(out.shape) != shape or out.device != self.device:

@@ -89,6 +89,18 @@ A 480i uyvy422 capture sent as fields, no host `yadif` in front of the tool:
              --deinterlace edge --field-order bff --deinterlace-fields both [effect flags] |
       ffmpeg -f rawvideo -pix_fmt rgb24 -s 720x480 -r 60000/1001 -i - out.mp4
 
+`--deliver-interlace tff|bff` delivers interlaced frames: every two consecutive finished frames are woven into one on the GPU
+(include/crtfx_interlace.h), behind the delivery resize and the pad and in front of the dither and the output format, the first frame of
+a pair giving the even rows (tff) or the odd rows (bff); `--deliver-lowpass linear|complex` filters every row vertically inside its own
+frame first, against line twitter.  With `--deinterlace-fields both` in front, a 29.97i tape runs through the chain at field rate and
+leaves as 29.97i, without a second ffmpeg process for `interlace` / `tinterlace`; the output holds half the chain's frames (an odd last
+one is woven with itself).  480i in, 480i out, for a DVD encoder:
+
+    ffmpeg -i capture_480i.avi -f rawvideo -pix_fmt uyvy422 - |
+      python -m pythoncrt_amd.cli --input - --width 720 --height 480 --fps 60 --output - --in-pix-fmt uyvy422 --out-pix-fmt uyvy422 \
+             --deinterlace edge --field-order bff --deinterlace-fields both --deliver-interlace bff --deliver-lowpass linear [effect flags] |
+      ffmpeg -f rawvideo -pix_fmt uyvy422 -s 720x480 -r 30000/1001 -i - -flags +ilme+ildct -field_order bb out.mpg
+
 `--in-lut FILE` / `--deliver-lut FILE` apply a 3D colour LUT (a `.cube` file, tetrahedral interpolation; include/crtfx_lut3d.h) on the
 GPU directly in front of the chain and directly behind it, at `--width x --height` and on the chain's pixels — the `lut3d=` of a second
 ffmpeg process and its round trip through host memory.  `--in-lut` brings a log-encoded or HDR source to display-referred video before
@@ -237,7 +249,28 @@ def add_output_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--deliver-lut", type=str, default="", metavar="FILE",
                    help="a .cube file (3D LUT, sizes 2..65, domain 0..1) applied to the finished frames on the GPU, directly behind the chain and in "
                         "front of the delivery resize, the pad and the dither (include/crtfx_lut3d.h: tetrahedral, 10-bit entries); default: none")
+    p.add_argument("--deliver-interlace", type=str, default="off", choices=["off", "tff", "bff"],
+                   help="weave every two consecutive finished frames into one interlaced frame on the GPU (include/crtfx_interlace.h), behind the "
+                        "delivery resize and the pad and in front of the dither and the output format: the first frame of a pair gives the even rows "
+                        "(tff) or the odd rows (bff); the output holds half the frames, an odd last one woven with itself (pass the field rate as "
+                        "--fps); off (default) = a progressive delivery")
+    p.add_argument("--deliver-lowpass", type=str, default="none", choices=["none", "linear", "complex"],
+                   help="vertical low-pass of every row inside its own frame before the weave, against line twitter: [1 2 1] / 4 (linear) or "
+                        "[-1 2 6 2 -1] / 8 held back from over-sharpening (complex); none (default) copies rows; needs --deliver-interlace")
     return p
+
+
+def interlace_from_args(a, deliver=None):
+    """(order, lowpass) of --deliver-interlace / --deliver-lowpass, or None for a progressive delivery.  `deliver` is deliver_size_from_args(a)."""
+    order, lowpass = getattr(a, "deliver_interlace", "off"), getattr(a, "deliver_lowpass", "none")
+    if order == "off":
+        if lowpass != "none":
+            raise SystemExit(f"--deliver-lowpass {lowpass} without --deliver-interlace tff | bff: there is nothing to filter")
+        return None
+    rows = deliver[0] if deliver is not None else int(a.height)
+    if 0 < rows < 2:
+        raise SystemExit(f"--deliver-interlace {order} with a delivery height of {rows}: a frame of one row has no two fields")
+    return order, lowpass
 
 
 def luts_from_args(a):
@@ -410,6 +443,7 @@ def main_sharded(a, rank: int, world: int) -> int:
     for flag, on in (("--in-crop-x / --in-crop-y / --in-crop-width / --in-crop-height", any(getattr(a, "in_crop_" + k, 0) for k in ("x", "y", "width", "height"))),
                      ("--deinterlace / --field-order / --deinterlace-fields", deinterlace_from_args(a) is not None),
                      ("--in-lut", bool(getattr(a, "in_lut", ""))), ("--deliver-lut", bool(getattr(a, "deliver_lut", ""))),
+                     ("--deliver-interlace / --deliver-lowpass", interlace_from_args(a) is not None),
                      ("--deliver-fit", getattr(a, "deliver_fit", "stretch") != "stretch"),
                      ("--deliver-pad-color", str(getattr(a, "deliver_pad_color", "0,0,0")) != "0,0,0")):
         if on:
@@ -569,6 +603,7 @@ def check_flags(a):
                          "narrowed to an 8-bit output are dithered; pass --chain-pix half and an 8-bit or rgb24 --out-pix-fmt")
     deint = deinterlace_from_args(a)
     deliver = deliver_size_from_args(a)
+    interlace_from_args(a, deliver)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("CRTFX_FORCE_DIST") == "1":
         if a.gui or not a.input or a.width <= 0 or a.height <= 0:
             raise SystemExit("pass --input, --width and --height")
@@ -593,9 +628,11 @@ def check_flags(a):
     return deliver, deep or half, None
 
 
-def open_output(a, fin, out_path: str, B: int, in_bytes: int, out_bytes: int, ratio: int = 1):
+def open_output(a, fin, out_path: str, B: int, in_bytes: int, out_bytes: int, ratio: int = 1, frames=None):
     """Open the output.  -> it, is each end a regular file (positional I/O; else sequential)?, pipe buffer sizes, [(offset, bytes)] per batch | None.
-    `B` counts delivery frames per batch, `ratio` of them per input frame (2 under --deinterlace-fields both; B is then even)."""
+    `B` counts the chain's frames per batch, `ratio` of them per input frame (2 under --deinterlace-fields both; B is then even).  `frames`
+    (DeliveryEnd.frames) gives the frames delivered for a batch of the chain's: under --deliver-interlace half of them, an odd last batch
+    rounded up (B is then even, so only the last batch can be odd)."""
     from .staging import _grow_pipe, _seekable
     in_pos = _seekable(fin) and a.input != "-"
     # opened with read access too (a MAP_SHARED, PROT_WRITE mapping needs O_RDWR).  --io mapped | auto only: an existing regular output behind a regular
@@ -612,17 +649,19 @@ def open_output(a, fin, out_path: str, B: int, in_bytes: int, out_bytes: int, ra
     out_plan = None
     if in_pos and out_pos:
         n_total = os.fstat(fin.fileno()).st_size // in_bytes * ratio
-        out_plan = [(k * B * out_bytes, min(B, n_total - k * B) * out_bytes) for k in range((n_total + B - 1) // B)] or None
+        frames = frames or (lambda m: m)
+        out_plan = [(k * frames(B) * out_bytes, frames(min(B, n_total - k * B)) * out_bytes) for k in range((n_total + B - 1) // B)] or None
         if presize and out_pos:
-            os.ftruncate(fout.fileno(), n_total * out_bytes)
+            os.ftruncate(fout.fileno(), (out_plan[-1][0] + out_plan[-1][1]) if out_plan else 0)
     return fout, in_pos, out_pos, pipes, out_plan
 
 
 def feed(pipe, source, end, reader, writer, NS: int, fout, timed: bool):
     """The feed loop: every batch of the reader is uploaded, run through [source] -> chain -> [delivery end] and downloaded to the writer, on three
-    streams chained by events.  `fout`: the output if a regular file.  Returns the frames enqueued, the timing events, the seconds per leg.
+    streams chained by events.  `fout`: the output if a regular file.  Returns the frames delivered, the timing events, the seconds per leg.
     The reader's batches count input frames; a source that deinterlaces to both fields (source.ratio = 2) makes two chain frames of each, and
-    everything behind it — frame indices, the writer, the return value — counts those."""
+    the frame indices count those.  The writer and the return value count DELIVERED frames: end.frames(m) of a batch of m chain frames, which
+    is m unless the delivery end interlaces."""
     import torch
     dev, Bs, in_bytes, out_bytes = pipe.device, reader.shape[0], reader.frame_bytes, end.frame_bytes
     ratio = 1 if source is None else source.ratio
@@ -635,7 +674,7 @@ def feed(pipe, source, end, reader, writer, NS: int, fout, timed: bool):
     end.slots(dev_out)                                              # what the egress plan reads, what is downloaded
     compute, s_up, s_down = torch.cuda.current_stream(dev), torch.cuda.Stream(dev), torch.cuda.Stream(dev)
     kernels_done, down_done = [None] * NS, [None] * NS      # per device slot: its batch's kernels (dev_in free again) / download (dev_out free again)
-    state, index, k, out_off, pend, marks = None, 0, 0, 0, None, []
+    state, index, delivered, k, out_off, pend, marks = None, 0, 0, 0, 0, None, []
     t_get = t_enq = t_slot = t_rel = 0.0
 
     def mark(stream, timing=timed):
@@ -650,7 +689,8 @@ def feed(pipe, source, end, reader, writer, NS: int, fout, timed: bool):
             if item is None:
                 break
             i, n, got = item                                            # a trailing partial frame is dropped, as ffmpeg's rawvideo demuxer does
-            m = n * ratio                                               # the frames the chain runs and the writer gets
+            m = n * ratio                                               # the frames the chain runs
+            md = end.frames(m)                                          # the frames the writer gets
             tt = time.perf_counter()
             if n:
                 d = k % NS
@@ -680,13 +720,13 @@ def feed(pipe, source, end, reader, writer, NS: int, fout, timed: bool):
                 tt = time.perf_counter()
                 s_down.wait_event(kd)
                 d0 = mark(s_down) if timed else None
-                writer.download(j, m, send, s_down)               # into the pinned slot, or straight into the registered output mapping
+                writer.download(j, md, send, s_down)               # into the pinned slot, or straight into the registered output mapping
                 dn = mark(s_down)
                 down_done[d] = dn
                 if timed:
-                    marks.append((u0, up, k0, kd, d0, dn, n, m))
-                writer.put(j, m, dn, out_off if fout is not None else None)
-                out_off += m * out_bytes
+                    marks.append((u0, up, k0, kd, d0, dn, n, md))
+                writer.put(j, md, dn, out_off if fout is not None else None)
+                out_off += md * out_bytes
             # a pinned input slot goes back once its upload has completed: the PREVIOUS batch's (long done), never the one just enqueued
             t_enq += time.perf_counter() - tt
             tt = time.perf_counter()
@@ -700,6 +740,7 @@ def feed(pipe, source, end, reader, writer, NS: int, fout, timed: bool):
             else:
                 reader.release(i)
             index += m
+            delivered += md
             k += 1
             if got < Bs * in_bytes:
                 break
@@ -708,13 +749,14 @@ def feed(pipe, source, end, reader, writer, NS: int, fout, timed: bool):
             reader.release(pend[1])
         writer.close()
     except BaseException:
-        abandon(dev, reader, writer, fout, index, out_bytes)
+        abandon(dev, reader, writer, fout, delivered, out_bytes)
         raise
-    return index, marks, (t_get, t_enq, t_slot, t_rel)
+    return delivered, marks, (t_get, t_enq, t_slot, t_rel)
 
 
 def abandon(dev, reader, writer, fout, index: int, out_bytes: int) -> None:
-    """The render died: the GPU is drained, the writer stopped, a regular output file `fout` cut back to the frames written (a prefix)."""
+    """The render died: the GPU is drained, the writer stopped, a regular output file `fout` cut back to the frames written (a prefix).
+    `index` counts delivered frames, as the writer does."""
     import contextlib
     import torch
     with contextlib.suppress(Exception):
@@ -783,22 +825,23 @@ def main(argv=None) -> int:
     B, NS = max(1, int(a.batch)), 3
     deint = deinterlace_from_args(a)                               # an interlaced input: every format then has a source end, rgb24 too
     ratio = 2 if deint is not None and deint[2] == "both" else 1    # delivery frames per input frame
-    if ratio == 2:
+    weave = interlace_from_args(a, deliver)                        # an interlaced delivery: whole pairs per batch
+    if ratio == 2 or weave is not None:
         B = max(2, B - B % 2)                                      # the chain's batch: both fields of B // 2 input frames
     Bs = B // ratio                                                # input frames per batch
     in_cube, deliver_cube = luts_from_args(a)                      # --in-lut: every format then has a source end, rgb24 too
     end = DeliveryEnd(dev, (h, w), pix, a.out_pix_fmt, a.out_matrix, a.out_range, a.out_chroma, deliver, a.deliver_filter, a.deliver_fit, pad_color_from_args(a),
-                      narrow=narrow, **({} if deliver_cube is None else {"lut": deliver_cube}))
+                      narrow=narrow, **({} if deliver_cube is None else {"lut": deliver_cube}), **({} if weave is None else {"interlace": weave}))
     crop = in_crop_from_args(a)                                    # a window of the input: an rgb24 input then has a source end too
     source = (SourceEnd(dev, (h, w), a.in_pix_fmt, a.in_matrix, a.in_range, a.in_chroma, (h, w), a.in_filter, crop, pix, widen=widen, deinterlace=deint,
                         **({} if in_cube is None else {"lut": in_cube}))
               if a.in_pix_fmt != "rgb24" or crop is not None or widen or deint is not None or in_cube is not None else None)    # half chain: an rgb24 input goes through a Widen
     in_bytes = h * w * 3 if source is None else source.frame_bytes
     t0 = time.perf_counter()
-    fout, in_pos, out_pos, pipes, out_plan = open_output(a, fin, out_path, B, in_bytes, end.frame_bytes, ratio)
+    fout, in_pos, out_pos, pipes, out_plan = open_output(a, fin, out_path, B, in_bytes, end.frame_bytes, ratio, end.frames)
     jobs = ((k * Bs * in_bytes if in_pos else None, Bs) for k in itertools.count())     # whole batches until the stream ends (the reader stops at a short read)
     reader = _Reader(fin, in_pos, jobs, (B, h, w, 3) if source is None else (Bs,) + source.frame_shape, in_bytes, slots=NS, io=a.io, autostart=False)
-    writer = _Writer(fout, out_pos, end.shape(B), end.frame_bytes, slots=NS, plan=out_plan, io=a.io)
+    writer = _Writer(fout, out_pos, end.shape(end.frames(B)), end.frame_bytes, slots=NS, plan=out_plan, io=a.io)
     t_pipe = time.perf_counter()                                    # the pipeline proper: first read issued ... last batch written (the --staging-report line)
     t_slots = t_pipe - t_start - t_imports - t_engine
     index, marks, waits = feed(pipe, source, end, reader, writer, NS, fout if out_pos else None, a.staging_report)

@@ -1,6 +1,7 @@
 // crtfx_edge.hip.h — what the deinterlace stages share (include/crtfx_deint.h, include/crtfx_adeint.h): the tags of the field modes and the
 // paths, the sample types with the quarter-code quantiser, the dword-multiple loads and stores of the vec paths, and EDGE's direction search.
-// crtfx_deint.hip and crtfx_adeint.hip include it; everything is inlined device code in crtfx_deint_impl, and no kernel is declared here.
+// crtfx_deint.hip and crtfx_adeint.hip include it, and crtfx_interlace.hip for the sample types and the loads and stores; everything is inlined
+// device code in crtfx_deint_impl, and no kernel is declared here.
 #ifndef CRTFX_EDGE_HIP_H
 #define CRTFX_EDGE_HIP_H
 

@@ -1,5 +1,5 @@
 // crtfx_frame_host.h — the host skeleton of the frame stages (crtfx_canvas.hip, crtfx_depth.hip, crtfx_deint.hip, crtfx_adeint.hip,
-// crtfx_lut3d.hip): RGB frames in HBM to RGB frames in HBM, and what surrounds their kernels and does not depend on what the kernels do.
+// crtfx_lut3d.hip, crtfx_interlace.hip): RGB frames in HBM to RGB frames in HBM, and what surrounds their kernels and does not depend on what the kernels do.
 // Host code only, and everything here is a template or sits in an unnamed namespace, so every translation unit that includes it gets a
 // copy of its own: the units still share no state.  The device guard and the error helpers are those of the format stages
 // (crtfx_stage_host.h).  Unlike the format and resize stages these answer n == 0 with CRTFX_OK and look at no pointer then.
@@ -34,7 +34,8 @@ struct Plan {
     int device = 0;
     size_t src_bytes = 0, dst_bytes = 0;       // of one frame
     int src_bps = 1, dst_bps = 1;               // bytes per sample
-    int frames_out = 1;                         // output frames per source frame
+    int frames_out = 1;                         // output frames per source frame ...
+    int frames_in = 1;                          // ... or rather per frames_in source frames: n frames give ceil(n / frames_in) * frames_out
     bool force_general = false;
     char plan[128] = "";
     std::string err;
@@ -52,7 +53,7 @@ struct Batch {
 
 struct Unit {
     static constexpr bool one_size = false;     // source and output frames have one size, and the stride message names it once
-    template <class A> static int group(const A&) { return 32768; }    // source frames per launch: grid.z
+    template <class A> static int group(const A&) { return 32768; }    // source frames per launch (grid.z); a multiple of the plan's frames_in
 };
 
 // ---- create: begin_create, the unit's own argument checks (check_size among them), then new_plan with what fills the handle ----
@@ -116,7 +117,7 @@ int run(typename U::H* p, const Batch& b, void* stream) {
     if (n < 0) return fail(p, CRTFX_E_INVALID, "n = %d frames", n);
     if (n == 0) { U::note_plan(p, U::vec_fits(p, b), 0); return CRTFX_OK; }
     if (!b.src || !b.dst) return fail(p, CRTFX_E_INVALID, "null frame pointer");
-    const size_t n_out = (size_t)n * p->frames_out;
+    const size_t n_out = ((size_t)n + p->frames_in - 1) / p->frames_in * p->frames_out;
     const uintptr_t sb = reinterpret_cast<uintptr_t>(b.src), db = reinterpret_cast<uintptr_t>(b.dst), pb = reinterpret_cast<uintptr_t>(b.prev);
     if ((p->src_bps == 2 && ((sb & 1u) || (n > 1 && (b.src_stride & 1u)))) || (p->dst_bps == 2 && ((db & 1u) || (n_out > 1 && (b.dst_stride & 1u)))))
         return fail(p, CRTFX_E_INVALID, "half frames need even bases and strides");
@@ -138,7 +139,7 @@ int run(typename U::H* p, const Batch& b, void* stream) {
     const int group = U::group(a);
     for (int f = 0; f < n; f += group) {
         a.src = static_cast<const uint8_t*>(b.src) + (size_t)f * b.src_stride;
-        a.dst = static_cast<uint8_t*>(b.dst) + (size_t)f * p->frames_out * b.dst_stride;
+        a.dst = static_cast<uint8_t*>(b.dst) + (size_t)f / p->frames_in * p->frames_out * b.dst_stride;
         U::launch(p, fits, a, f, (unsigned)(n - f < group ? n - f : group), st);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return fail(p, CRTFX_E_HIP, "%s launch: %s", U::name, hipGetErrorString(e));

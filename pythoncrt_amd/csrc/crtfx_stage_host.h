@@ -3,7 +3,7 @@
 // sits in an unnamed namespace, so every translation unit that includes it gets a copy of its own: the units still share no state.  The resize
 // stages' skeleton (crtfx_resize_host.h: crtfx_ingest.hip, crtfx_resize16.hip, crtfx_resample.hip) takes DeviceGuard, create_err and fail from
 // here and nothing else; the frame stages' skeleton (crtfx_frame_host.h: crtfx_canvas.hip, crtfx_depth.hip, crtfx_deint.hip, crtfx_adeint.hip,
-// crtfx_lut3d.hip) takes those three and begin_create.
+// crtfx_lut3d.hip, crtfx_interlace.hip) takes those three and begin_create.
 //
 // A unit brings its kernels, its Args, a plan `struct Plan : StagePlan { Args args{}; }`, its handle types (the plan itself or structures
 // derived from it) and a structure U of static members that the templates below take as a parameter, so that every call is a direct one:

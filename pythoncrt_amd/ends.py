@@ -6,6 +6,7 @@ from .adeint import METHOD as ADAPTIVE, AdaptiveDeinterlace
 from .canvas import Canvas, fit_crop, fit_pad
 from .deint import Deinterlace
 from .depth import Narrow, Widen
+from .interlace import Interlace
 from .lut3d import Lut3D
 
 
@@ -110,13 +111,19 @@ class DeliveryEnd:
     (include/crtfx_depth.h) writes the uint8 frames the egress plan reads — or, for "rgb24", the frames that are downloaded; the dither's
     coordinates are those of the delivered frame.  `lut` is None or a Cube: a Lut3D (include/crtfx_lut3d.h) at the render size and on
     `pix` is then the FIRST stage, in front of the delivery resize, the Canvas, the Narrow and the egress plan — a pad colour is not
-    transformed and the dither stays last.  Everything downstream is in frames of `frame_bytes`, batches of `shape(B)`."""
+    transformed and the dither stays last.  `interlace` is None or (order, lowpass): an Interlace (include/crtfx_interlace.h) at the
+    DELIVERY size and on `pix` then stands behind the delivery resize and the Canvas — a vertical resize would mix the fields — and in front
+    of the Narrow and the egress plan: the low-pass runs at the chain's precision, the dither's coordinates are those of the delivered
+    frame and the dither stays last.  It weaves two finished frames into one, an odd last frame of a run with itself: from it on every
+    buffer holds `frames(B)` = ceil(B / 2) frames, and run(d, m) returns frames(m).  Known limit: the chroma rows of a 4:2:0 delivery are
+    formed by the egress plan as a progressive frame's are, so they mix the two fields; 4:2:2, 4:4:4 and rgb24 deliveries have no such
+    pairing.  Everything downstream is in frames of `frame_bytes`, batches of `shape(frames(B))`."""
 
     def __init__(self, device, render_hw, pix, out_pix_fmt, out_matrix, out_range, out_chroma, deliver, deliver_filter,
-                 deliver_fit="stretch", pad_color=(0, 0, 0), narrow=None, lut=None):
+                 deliver_fit="stretch", pad_color=(0, 0, 0), narrow=None, lut=None, interlace=None):
         self.device, self.pix = device, pix
         self.size = tuple(deliver) if deliver is not None else tuple(render_hw)
-        self.resize = self.canvas = self.narrow = self.lut = None
+        self.resize = self.canvas = self.narrow = self.lut = self.interlace = None
         self.stages = []                 # (plan, the size of the frames it writes), in order, in front of the egress plan
         if lut is not None:
             self.lut = Lut3D(device, tuple(render_hw), lut, dtype=pix)
@@ -138,13 +145,21 @@ class DeliveryEnd:
         elif deliver is not None:
             self.resize = resize_plan(device, render_hw, self.size, deliver_filter, pix)
             self.stages.append((self.resize, self.size))
+        if interlace is not None:
+            self.interlace = Interlace(device, self.size, order=interlace[0], lowpass=interlace[1], dtype=pix)
+            self.stages.append((self.interlace, self.size))
         if narrow is not None:
             self.narrow = Narrow(device, self.size, dither=narrow)
             self.stages.append((self.narrow, self.size))
         self.egress = formats.egress_plan(device, self.size, out_pix_fmt, out_matrix, out_range, out_chroma)
         self.frame_bytes = self.size[0] * self.size[1] * 3 if self.egress is None else self.egress.frame_bytes
 
+    def frames(self, m: int) -> int:
+        """The frames delivered for m frames of the chain: m, or ceil(m / 2) behind an Interlace."""
+        return m if self.interlace is None else -(-m // self.interlace.frames_in)
+
     def shape(self, B: int):
+        """Of a batch of B DELIVERED frames (frames(the chain's batch))."""
         return (B,) + self.size + (3,) if self.egress is None else (B, self.frame_bytes)
 
     def slots(self, dev_out):
@@ -152,18 +167,24 @@ class DeliveryEnd:
         import torch
         B = int(dev_out[0].shape[0])
         self.out = self.fin = self.send = dev_out
-        self.bufs = [[torch.empty((B,) + hw + (3,), dtype=torch.uint8 if st is self.narrow else self.pix, device=self.device) for _ in dev_out]
-                     for st, hw in self.stages]
+        # the Interlace and every stage behind it write frames(B) frames
+        behind = [any(st is self.interlace for st, _ in self.stages[:i + 1]) for i in range(len(self.stages))]
+        self.bufs = [[torch.empty((self.frames(B) if behind[i] else B,) + hw + (3,), dtype=torch.uint8 if st is self.narrow else self.pix,
+                                  device=self.device) for _ in dev_out]
+                     for i, (st, hw) in enumerate(self.stages)]
         if self.bufs:
             self.fin = self.send = self.bufs[-1]
         if self.egress is not None:
-            self.send = [torch.empty(self.shape(B), dtype=torch.uint8, device=self.device) for _ in dev_out]
+            self.send = [torch.empty(self.shape(self.frames(B)), dtype=torch.uint8, device=self.device) for _ in dev_out]
         return self.fin, self.send
 
     def run(self, d: int, n: int):
-        """Slot d's stages over its first n frames; returns the frames to download.  The caller has awaited the slot's last download."""
+        """Slot d's stages over its first n frames; returns the frames to download, frames(n) of them.  The caller has awaited the slot's
+        last download."""
         x = self.out[d][:n]
         for (stage, _), buf in zip(self.stages, self.bufs):
+            if stage is self.interlace:
+                n = self.frames(n)
             x = stage.run(x, out=buf[d][:n])
         if self.egress is not None:
             self.egress.run(self.fin[d][:n], out=self.send[d][:n])

@@ -150,7 +150,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                    in_filter: str = "bilinear", deliver_filter: str = "bilinear", in_crop: Optional[Tuple[int, int, int, int]] = None,
                    deliver_fit: str = "stretch", deliver_pad_color: Tuple[int, int, int] = (0, 0, 0), chain_pix: str = "auto",
                    dither: str = "none", deinterlace: str = "off", field_order: str = "tff", deinterlace_fields: str = "first",
-                   in_lut=None, deliver_lut=None, **io_keywords) -> int:
+                   in_lut=None, deliver_lut=None, deliver_interlace: str = "off", deliver_lowpass: str = "none", **io_keywords) -> int:
     """Render every frame of `frame_iter` (H x W x 3 uint8 RGB arrays) and hand the finished uint8 frames to `write_frame` in order.
     Effect keywords: the names, meaning and defaults of process_video / the CLI (ref:864-911, :1155-1206); the caller applies the clamps of
     ref:1225-1266 as the reference's `main` does (`pythoncrt_amd.cli.settings_from_args` restates them).  Returns the number of frames written.
@@ -273,6 +273,22 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     domain 0..1 and sizes 2..65 are taken.  `None` (default) creates no plan and no buffer: the path as it was.  Refused with ValueError
     before a device is touched: a cube that cannot be read or is malformed (the message names the file and the line), a value that is
     neither a path nor a Cube, and `in_lut` with `resize_on="host"`.
+    `deliver_interlace="tff"` / `"bff"` delivers interlaced frames (1080i / 576i / 480i for DVD, broadcast, an interlaced encoder
+    (`-flags +ilme+ildct`) or a real CRT): an Interlace (include/crtfx_interlace.h) weaves every two consecutive finished frames into one on
+    the device, the first of a pair giving the even rows under "tff" and the odd rows under "bff" — what `interlace` / `tinterlace` in a
+    second ffmpeg process did.  It is the delivery pair of `deinterlace_fields="both"`: a 29.97i source runs through the chain at field
+    rate and leaves as 29.97i.  It stands at the DELIVERY size and on the chain's pixel type, behind the delivery resize and the Canvas (a
+    vertical resize would mix the fields) and in front of the Narrow and the egress plan: the dither's coordinates are those of the
+    delivered frame and the dither stays last.  `deliver_lowpass` filters every row vertically inside its own frame before the weave,
+    against line twitter: "linear" is [1 2 1] / 4, "complex" [-1 2 6 2 -1] / 8 held back from over-sharpening; "none" (default) copies
+    rows as bits.  The chain's batch B is `batch` taken even and at least 2, as under `deinterlace_fields="both"`, and a pair never
+    straddles a batch: a batch with an odd frame count has its last frame woven with itself.  That happens at the end of the stream, and
+    at a change of source size in a mixed rgb24 stream when no deinterlacer doubles the frames.  `written`, `progress_cb`, the return
+    value and `total_frames` count DELIVERED frames; the chain's frame indices and its clock are unchanged: pass the field rate as
+    `fps_out`.  "off" (default) builds no plan and no buffer: the path as it was.  Known limit: the chroma rows of a 4:2:0 delivery are
+    formed by the egress plan as a progressive frame's are, so they mix the two fields; 4:2:2, 4:4:4 and rgb24 deliveries have no such
+    pairing.  Refused with ValueError before a device is touched: an unknown value of either keyword; `deliver_lowpass` other than "none"
+    with "off" (there is nothing to filter); a delivery height below 2.
     If `frame_iter` or `write_frame` raises, the GPU work already queued is drained (device synchronize) before the exception leaves this
     function, so that the staging buffers are not freed under a running copy."""
     import os
@@ -358,6 +374,17 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                          "resize to filter")
     if deliver_fit != "stretch" and deliver is None:
         raise ValueError(f"deliver_fit={deliver_fit!r} without a deliver_size that differs from the render size: there is nothing to fit")
+    from .interlace import LOWPASS
+    from .interlace import ORDERS as WEAVE_ORDERS
+    if deliver_interlace != "off" and deliver_interlace not in WEAVE_ORDERS:
+        raise ValueError(f"deliver_interlace must be 'off' or one of {', '.join(WEAVE_ORDERS)}, got {deliver_interlace!r}")
+    if deliver_lowpass not in LOWPASS:
+        raise ValueError(f"deliver_lowpass must be one of {', '.join(LOWPASS)}, got {deliver_lowpass!r}")
+    if deliver_interlace == "off" and deliver_lowpass != "none":
+        raise ValueError(f"deliver_lowpass={deliver_lowpass!r} with deliver_interlace='off': there is nothing to filter")
+    weave = None if deliver_interlace == "off" else (deliver_interlace, deliver_lowpass)
+    if weave is not None and (deliver or (int(out_h), int(out_w)))[0] < 2:
+        raise ValueError(f"deliver_interlace={deliver_interlace!r}: a delivered frame of {(deliver or (int(out_h), int(out_w)))[0]} row(s) has no two fields")
     from .cube import as_cube
     if in_lut is not None and resize_on == "host":
         raise ValueError("resize_on='host' cannot be combined with in_lut: the cube is applied on the device, behind the device's resize")
@@ -367,8 +394,8 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         raise RuntimeError("no ROCm device visible; pythoncrt_amd has no CPU fallback")
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     h, w, B = int(out_h), int(out_w), max(1, int(batch))
-    if ratio == 2:
-        B = max(2, B - B % 2)                                                  # the chain's batch: both fields of B // 2 source frames
+    if ratio == 2 or weave is not None:
+        B = max(2, B - B % 2)                                                  # the chain's batch: both fields of B // 2 source frames, whole pairs for the Interlace
     Bs = B // ratio                                                            # source frames per batch
     rs = RenderSettings(
         scanline_strength=float(scanline_strength), triad_strength=float(triad_strength), triad_gamma=float(triad_gamma),
@@ -393,8 +420,8 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     NS = 2
     pin_in = [torch.empty((B, h, w, 3), dtype=torch.uint8).pin_memory() for _ in range(NS)] if in_pix_fmt == "rgb24" and not widen and deint is None and in_cube is None else None   # else: a SourceEnd's own
     end = DeliveryEnd(dev, (h, w), pix, out_pix_fmt, out_matrix, out_range, out_chroma, deliver, deliver_filter, deliver_fit, pad_color,
-                      narrow=narrow, **({} if deliver_cube is None else {"lut": deliver_cube}))
-    pin_out = [torch.empty(end.shape(B), dtype=torch.uint8).pin_memory() for _ in range(NS)]    # what is downloaded and handed to the writer
+                      narrow=narrow, **({} if deliver_cube is None else {"lut": deliver_cube}), **({} if weave is None else {"interlace": weave}))
+    pin_out = [torch.empty(end.shape(end.frames(B)), dtype=torch.uint8).pin_memory() for _ in range(NS)]    # what is downloaded and handed to the writer
     dev_in = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]
     dev_out = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]
     end.slots(dev_out)
@@ -498,7 +525,8 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                 src.up_done[d] = up
                 compute.wait_event(up)
                 # dev_in[d]: its last upload (two batches ago) was awaited by `compute` then, its last readers ran on `compute`
-                m = n * ratio                        # the frames the chain runs and the writer gets: n source frames, `ratio` each
+                m = n * ratio                        # the frames the chain runs: n source frames, `ratio` each
+                md = end.frames(m)                   # the frames the writer gets: m, or ceil(m / 2) woven ones
                 if key != last_key and src is not direct:
                     src.restart()                    # deinterlace="adaptive": the frame before this batch's first is not its previous frame
                 last_key = key
@@ -513,7 +541,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                 # pin_out[d] was drained one iteration ago (drain below runs before the next batch is enqueued into the same slot)
                 s_down.wait_event(kd)
                 with torch.cuda.stream(s_down):
-                    pin_out[d][:m].copy_(send, non_blocking=True)
+                    pin_out[d][:md].copy_(send, non_blocking=True)
                     dn = torch.cuda.Event()
                     dn.record(s_down)
                 down_done[d] = dn
@@ -523,7 +551,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                 drain(pending)
                 pending = None
             if n:
-                pending = (d, m, dn)
+                pending = (d, md, dn)
             k += 1
         if pending is not None:
             drain(pending)
