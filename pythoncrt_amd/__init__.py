@@ -17,6 +17,7 @@
     from pythoncrt_amd import Deinterlace         # yadif's place: two fields woven into a frame become one progressive frame, or one per field
     from pythoncrt_amd import AdaptiveDeinterlace # ... motion-adaptive: the other field woven in where the picture stood still, "edge" where it moved
     from pythoncrt_amd import Interlace           # interlace / tinterlace's place: two finished frames woven into one 1080i / 576i / 480i frame, with a low-pass
+    from pythoncrt_amd import Signal              # the cable: an NTSC-like composite / S-Video encode and decode of every row: bleed, dot crawl, rainbows
     from pythoncrt_amd import Lut3D, Cube         # lut3d=: a .cube colour LUT applied with tetrahedral interpolation, uint8 or half frames
 
 See DESIGN.md (path, kernels, roofline) and INTEGRATION.md (how the reference binds to it).
@@ -37,10 +38,11 @@ from .lut3d import Lut3D
 from .resize16 import ResizeHalf
 from .resample import Resample
 from .render import iter_deep444, iter_rgb24, iter_yuv420, iter_yuv422, process_frames
+from .signal import Signal
 from .sited import EgressSited, UnpackSited
 from .unpack import UnpackYuv
 from .yuv422 import EgressYuv422, UnpackYuv422
 
 __all__ = ["DeviceState", "TriadMask", "VignetteMask", "apply_crt_effect", "apply_static_effects", "make_triad_mask", "make_vignette",
            "process_frames", "iter_rgb24", "iter_yuv420", "IngestResize", "EgressYuv", "UnpackYuv", "EgressYuv10", "UnpackYuv10",
-           "iter_yuv422", "EgressYuv422", "UnpackYuv422", "iter_deep444", "EgressDeep444", "UnpackDeep444", "UnpackSited", "EgressSited", "ResizeHalf", "Resample", "Canvas", "Widen", "Narrow", "Deinterlace", "AdaptiveDeinterlace", "Lut3D", "Cube", "Interlace"]
+           "iter_yuv422", "EgressYuv422", "UnpackYuv422", "iter_deep444", "EgressDeep444", "UnpackDeep444", "UnpackSited", "EgressSited", "ResizeHalf", "Resample", "Canvas", "Widen", "Narrow", "Deinterlace", "AdaptiveDeinterlace", "Lut3D", "Cube", "Interlace", "Signal"]

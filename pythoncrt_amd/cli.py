@@ -101,6 +101,18 @@ one is woven with itself).  480i in, 480i out, for a DVD encoder:
              --deinterlace edge --field-order bff --deinterlace-fields both --deliver-interlace bff --deliver-lowpass linear [effect flags] |
       ffmpeg -f rawvideo -pix_fmt uyvy422 -s 720x480 -r 30000/1001 -i - -flags +ilme+ildct -field_order bb out.mpg
 
+`--in-signal composite|svideo` sends every input frame through the cable that fed the tube (include/crtfx_signal.h): every row is encoded
+to an NTSC-like signal and decoded again on the GPU, before anything else sees it — colour that bleeds sideways and, under `composite`, dot
+crawl on colour edges and rainbow fringes on fine luma detail; `svideo` keeps luma and chroma apart.  One pixel is one sample at four
+times the colour subcarrier (about 754 to an active line), so pass an SD-width input and let `--deliver-width` / a larger render happen
+behind it.  `--signal-chroma sharp|soft` is the decoder's chroma low-pass and `--signal-crawl on|off` turns the subcarrier by 180 degrees
+per frame as well as per line (on, the default: dot crawl).  NTSC-like only: no PAL, no RF noise.  A 480i capture over composite:
+
+    ffmpeg -i capture_480i.avi -f rawvideo -pix_fmt uyvy422 - |
+      python -m pythoncrt_amd.cli --input - --width 720 --height 480 --fps 60 --output - --in-pix-fmt uyvy422 \
+             --in-signal composite --signal-chroma soft --deinterlace edge --deinterlace-fields both [effect flags] |
+      ffmpeg -f rawvideo -pix_fmt rgb24 -s 720x480 -r 60000/1001 -i - out.mp4
+
 `--in-lut FILE` / `--deliver-lut FILE` apply a 3D colour LUT (a `.cube` file, tetrahedral interpolation; include/crtfx_lut3d.h) on the
 GPU directly in front of the chain and directly behind it, at `--width x --height` and on the chain's pixels — the `lut3d=` of a second
 ffmpeg process and its round trip through host memory.  `--in-lut` brings a log-encoded or HDR source to display-referred video before
@@ -379,7 +391,27 @@ def add_input_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
                    help="a .cube file (3D LUT, sizes 2..65, domain 0..1) applied to the source frames on the GPU at --width x --height, directly in "
                         "front of the chain: behind the resize and, under --chain-pix half, behind the widening (include/crtfx_lut3d.h: "
                         "tetrahedral, 10-bit entries) — log footage or HDR10 brought to display-referred video; default: none")
+    p.add_argument("--in-signal", type=str, default="rgb", choices=["rgb", "composite", "svideo"],
+                   help="send every input frame through an NTSC-like composite or S-Video encode and decode on the GPU (include/crtfx_signal.h), at "
+                        "the input's size and in front of the deinterlacer, the crop and the resize: colour bleed and, under composite, dot crawl "
+                        "and rainbow fringes; one pixel is one sample at four times the colour subcarrier, so pass an SD-width input; rgb (default) "
+                        "= no signal")
+    p.add_argument("--signal-chroma", type=str, default="sharp", choices=["sharp", "soft"],
+                   help="the decoder's chroma low-pass under --in-signal: [1 2 3 4 3 2 1] / 16 (sharp, default) or [1 2 .. 8 .. 2 1] / 64 (soft)")
+    p.add_argument("--signal-crawl", type=str, default="on", choices=["on", "off"],
+                   help="turn the subcarrier by 180 degrees per frame as well as per line (on, default: dot crawl) or per line only (off); needs "
+                        "--in-signal")
     return p
+
+
+def signal_from_args(a):
+    """(signal, chroma, crawl) of --in-signal / --signal-chroma / --signal-crawl, or None for an input that came without a cable."""
+    signal, chroma, crawl = getattr(a, "in_signal", "rgb"), getattr(a, "signal_chroma", "sharp"), getattr(a, "signal_crawl", "on")
+    if signal == "rgb":
+        if chroma != "sharp" or crawl != "on":
+            raise SystemExit(f"--signal-chroma {chroma} / --signal-crawl {crawl} without --in-signal composite | svideo: there is no signal to decode")
+        return None
+    return signal, chroma, crawl == "on"
 
 
 def deinterlace_from_args(a):
@@ -442,6 +474,7 @@ def main_sharded(a, rank: int, world: int) -> int:
                          "run one process, or scale behind it")
     for flag, on in (("--in-crop-x / --in-crop-y / --in-crop-width / --in-crop-height", any(getattr(a, "in_crop_" + k, 0) for k in ("x", "y", "width", "height"))),
                      ("--deinterlace / --field-order / --deinterlace-fields", deinterlace_from_args(a) is not None),
+                     ("--in-signal / --signal-chroma / --signal-crawl", signal_from_args(a) is not None),
                      ("--in-lut", bool(getattr(a, "in_lut", ""))), ("--deliver-lut", bool(getattr(a, "deliver_lut", ""))),
                      ("--deliver-interlace / --deliver-lowpass", interlace_from_args(a) is not None),
                      ("--deliver-fit", getattr(a, "deliver_fit", "stretch") != "stretch"),
@@ -602,6 +635,7 @@ def check_flags(a):
         raise SystemExit(f"--dither {a.dither} with --chain-pix {getattr(a, 'chain_pix', 'auto')} and --out-pix-fmt {a.out_pix_fmt}: only half frames "
                          "narrowed to an 8-bit output are dithered; pass --chain-pix half and an 8-bit or rgb24 --out-pix-fmt")
     deint = deinterlace_from_args(a)
+    signal_from_args(a)
     deliver = deliver_size_from_args(a)
     interlace_from_args(a, deliver)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("CRTFX_FORCE_DIST") == "1":
@@ -707,6 +741,7 @@ def feed(pipe, source, end, reader, writer, NS: int, fout, timed: bool):
                 k0 = mark(compute) if timed else None
                 # on the compute stream and counted with the kernels (k0 ... kd): dev_in[d]'s last reader (batch k - NS) ran on this stream
                 if source is not None:
+                    source.index = index // ratio                    # the batch's first input frame in the stream: --in-signal's t
                     source.convert(d, n, dev_in[d][:m])
                 _, state = pipe.run(dev_in[d][:m], first_index=index, state=state, out=dev_out[d][:m])
                 send = end.run(d, m)
@@ -833,9 +868,10 @@ def main(argv=None) -> int:
     end = DeliveryEnd(dev, (h, w), pix, a.out_pix_fmt, a.out_matrix, a.out_range, a.out_chroma, deliver, a.deliver_filter, a.deliver_fit, pad_color_from_args(a),
                       narrow=narrow, **({} if deliver_cube is None else {"lut": deliver_cube}), **({} if weave is None else {"interlace": weave}))
     crop = in_crop_from_args(a)                                    # a window of the input: an rgb24 input then has a source end too
+    cable = signal_from_args(a)                                    # --in-signal: every format then has a source end, rgb24 too
     source = (SourceEnd(dev, (h, w), a.in_pix_fmt, a.in_matrix, a.in_range, a.in_chroma, (h, w), a.in_filter, crop, pix, widen=widen, deinterlace=deint,
-                        **({} if in_cube is None else {"lut": in_cube}))
-              if a.in_pix_fmt != "rgb24" or crop is not None or widen or deint is not None or in_cube is not None else None)    # half chain: an rgb24 input goes through a Widen
+                        **({} if in_cube is None else {"lut": in_cube}), **({} if cable is None else {"signal": cable}))
+              if a.in_pix_fmt != "rgb24" or crop is not None or widen or deint is not None or in_cube is not None or cable is not None else None)    # half chain: an rgb24 input goes through a Widen
     in_bytes = h * w * 3 if source is None else source.frame_bytes
     t0 = time.perf_counter()
     fout, in_pos, out_pos, pipes, out_plan = open_output(a, fin, out_path, B, in_bytes, end.frame_bytes, ratio, end.frames)

@@ -8,6 +8,7 @@ from .deint import Deinterlace
 from .depth import Narrow, Widen
 from .interlace import Interlace
 from .lut3d import Lut3D
+from .signal import Signal
 
 
 def depth_stages(in_pix_fmt: str, out_pix_fmt: str, chain_pix: str = "auto", dither: str = "none"):
@@ -44,14 +45,22 @@ class SourceEnd(StagingSlots):
     and restart() starts a new history (the frames that follow are not the continuation of those converted before).  `ratio` is the
     frames it writes per source frame (1 without it): the staged slots hold SOURCE frames and convert(d, n, dst) writes n * ratio frames.
     `lut` is None or a Cube: a Lut3D (include/crtfx_lut3d.h) at the render size and on the CHAIN's pixel type is then the last stage,
-    behind the resize and behind the Widen, and writes the chain's input — for an rgb24 frame at render size the only one."""
+    behind the resize and behind the Widen, and writes the chain's input — for an rgb24 frame at render size the only one.
+    `signal` is None or (signal, chroma, crawl): a Signal (include/crtfx_signal.h) then stands directly behind the source plan, at src_hw
+    and on `dtype`, in front of the Deinterlace, the Canvas, the resize, the Widen and the Lut3D — the cable carried the fields and the
+    source's own samples, one pixel being one sample at four times the colour subcarrier — for an rgb24 frame at render size the only
+    stage.  Its frame index t is the source frame's index in the stream: the caller sets `index` to that of the batch's first frame
+    before convert() (0 until it does); several ends of one stream (a mixed-size rgb24 source) are each told."""
 
     def __init__(self, device, render_hw, in_pix_fmt, in_matrix, in_range, in_chroma, src_hw, in_filter, crop=None, dtype=None, widen=False,
-                 deinterlace=None, lut=None):
+                 deinterlace=None, lut=None, signal=None):
         import torch
         self.device, self.src_hw = device, tuple(src_hw)
         self.dtype = torch.uint8 if dtype is None or widen else dtype      # widen: `dtype` is the chain's, the stages in front of it run on uint8
         self.plan = formats.source_plan(device, self.src_hw, in_pix_fmt, in_matrix, in_range, in_chroma)
+        self.signal, self.index = None, 0
+        if signal is not None:
+            self.signal = Signal(device, self.src_hw, signal=signal[0], chroma=signal[1], crawl=signal[2], dtype=self.dtype)
         self.deint, self.ratio, self.adaptive = None, 1, False
         if deinterlace is not None:
             method, order, fields = deinterlace
@@ -70,7 +79,7 @@ class SourceEnd(StagingSlots):
         self.frame_bytes = formats.frame_bytes(*self.src_hw, in_pix_fmt) if self.plan is None else self.plan.frame_bytes
         self.frame_shape = self.src_hw + (3,) if self.plan is None else (self.frame_bytes,)
         # the stages present, each with the size of the RGB frames it writes; the last one writes the chain's input
-        self.stages = [(st, hw) for st, hw in ((self.plan, self.src_hw), (self.deint, self.src_hw), (self.canvas, cut),
+        self.stages = [(st, hw) for st, hw in ((self.plan, self.src_hw), (self.signal, self.src_hw), (self.deint, self.src_hw), (self.canvas, cut),
                                                     (self.resize, tuple(render_hw)), (self.widen, tuple(render_hw)),
                                                     (self.lut, tuple(render_hw))) if st is not None]
 
@@ -92,7 +101,7 @@ class SourceEnd(StagingSlots):
             if stage is self.deint:
                 n *= self.ratio
             run = stage.push if self.adaptive and stage is self.deint else stage.run      # the adaptive plan keeps the last frame of the batch before
-            x = run(x, out=dst if i == len(self.stages) - 1 else self.mid[i][d][:n])
+            x = run(x, out=dst if i == len(self.stages) - 1 else self.mid[i][d][:n], **({"index": self.index} if stage is self.signal else {}))
 
     def restart(self):
         """The next batch converted does not continue the one before it: an AdaptiveDeinterlace forgets its kept frame.  Nothing otherwise."""

@@ -150,7 +150,8 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                    in_filter: str = "bilinear", deliver_filter: str = "bilinear", in_crop: Optional[Tuple[int, int, int, int]] = None,
                    deliver_fit: str = "stretch", deliver_pad_color: Tuple[int, int, int] = (0, 0, 0), chain_pix: str = "auto",
                    dither: str = "none", deinterlace: str = "off", field_order: str = "tff", deinterlace_fields: str = "first",
-                   in_lut=None, deliver_lut=None, deliver_interlace: str = "off", deliver_lowpass: str = "none", **io_keywords) -> int:
+                   in_lut=None, deliver_lut=None, deliver_interlace: str = "off", deliver_lowpass: str = "none",
+                   in_signal: str = "rgb", signal_chroma: str = "sharp", signal_crawl: bool = True, **io_keywords) -> int:
     """Render every frame of `frame_iter` (H x W x 3 uint8 RGB arrays) and hand the finished uint8 frames to `write_frame` in order.
     Effect keywords: the names, meaning and defaults of process_video / the CLI (ref:864-911, :1155-1206); the caller applies the clamps of
     ref:1225-1266 as the reference's `main` does (`pythoncrt_amd.cli.settings_from_args` restates them).  Returns the number of frames written.
@@ -289,6 +290,21 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     formed by the egress plan as a progressive frame's are, so they mix the two fields; 4:2:2, 4:4:4 and rgb24 deliveries have no such
     pairing.  Refused with ValueError before a device is touched: an unknown value of either keyword; `deliver_lowpass` other than "none"
     with "off" (there is nothing to filter); a delivery height below 2.
+    `in_signal="composite"` / `"svideo"` sends every source frame through the cable that fed the tube: a Signal (include/crtfx_signal.h)
+    encodes every row to an NTSC-like signal and decodes it again on the device — colour that bleeds sideways and, under "composite", dot
+    crawl on colour edges and rainbow fringes on fine luma detail; "svideo" keeps luma and chroma apart and only narrows the chroma — what
+    a second ffmpeg or shader pass in front of this project did.  One pixel is one sample at 4 x fsc (four times the colour subcarrier,
+    about 754 samples to an active line), so feed SD-width sources (`in_size`, or SD rgb24 frames); the resize to the render size is
+    behind the stage.  It stands directly behind the source plan, at the source's own size and sample type, in front of the Deinterlace,
+    `in_crop`'s Canvas, the resize, the Widen and `in_lut`: the cable carried the fields and the source's samples.  Every source then goes
+    through a source end, as under `in_lut` — an rgb24 frame at render size through one whose only stage is the Signal.
+    `signal_chroma` is the decoder's chroma low-pass, "sharp" (default: [1 2 3 4 3 2 1] / 16) or "soft" ([1 2 .. 8 .. 2 1] / 64);
+    `signal_crawl` (default True) turns the subcarrier by 180 degrees per frame as well as per line, counted in SOURCE frames from the
+    first one read, across changes of source size too.  "rgb" (default) builds no plan and no buffer: the path as it was.  Stated limits:
+    NTSC-like only (no PAL, no burst-axis rotation, no RF noise); the rows of a woven interlaced frame are taken as consecutive lines; the
+    chroma rows of a 4:2:0 source are formed in front of the stage by its source plan.  Refused with ValueError before a device is
+    touched: an unknown value of the three keywords; `signal_chroma` or `signal_crawl` off its default with "rgb" (there is no signal);
+    `resize_on="host"`.
     If `frame_iter` or `write_frame` raises, the GPU work already queued is drained (device synchronize) before the exception leaves this
     function, so that the staging buffers are not freed under a running copy."""
     import os
@@ -385,6 +401,19 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     weave = None if deliver_interlace == "off" else (deliver_interlace, deliver_lowpass)
     if weave is not None and (deliver or (int(out_h), int(out_w)))[0] < 2:
         raise ValueError(f"deliver_interlace={deliver_interlace!r}: a delivered frame of {(deliver or (int(out_h), int(out_w)))[0]} row(s) has no two fields")
+    from .signal import CHROMAS, SIGNALS
+    if not isinstance(in_signal, str) or (in_signal != "rgb" and in_signal not in SIGNALS):
+        raise ValueError(f"in_signal must be 'rgb' or one of {', '.join(SIGNALS)}, got {in_signal!r}")
+    if not isinstance(signal_chroma, str) or signal_chroma not in CHROMAS:
+        raise ValueError(f"signal_chroma must be one of {', '.join(CHROMAS)}, got {signal_chroma!r}")
+    if not isinstance(signal_crawl, bool):
+        raise ValueError(f"signal_crawl must be True or False, got {signal_crawl!r}")
+    if in_signal == "rgb" and (signal_chroma != "sharp" or not signal_crawl):
+        raise ValueError(f"signal_chroma={signal_chroma!r} / signal_crawl={signal_crawl!r} with in_signal='rgb': there is no signal to decode")
+    if in_signal != "rgb" and resize_on == "host":
+        raise ValueError(f"resize_on='host' cannot be combined with in_signal={in_signal!r}: the signal is formed on the device, at the source's size, "
+                         "in front of the device's resize")
+    cable = None if in_signal == "rgb" else (in_signal, signal_chroma, signal_crawl)
     from .cube import as_cube
     if in_lut is not None and resize_on == "host":
         raise ValueError("resize_on='host' cannot be combined with in_lut: the cube is applied on the device, behind the device's resize")
@@ -418,7 +447,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     total = max(1, int(total_frames)) if total_frames else None
 
     NS = 2
-    pin_in = [torch.empty((B, h, w, 3), dtype=torch.uint8).pin_memory() for _ in range(NS)] if in_pix_fmt == "rgb24" and not widen and deint is None and in_cube is None else None   # else: a SourceEnd's own
+    pin_in = [torch.empty((B, h, w, 3), dtype=torch.uint8).pin_memory() for _ in range(NS)] if in_pix_fmt == "rgb24" and not widen and deint is None and in_cube is None and cable is None else None   # else: a SourceEnd's own
     end = DeliveryEnd(dev, (h, w), pix, out_pix_fmt, out_matrix, out_range, out_chroma, deliver, deliver_filter, deliver_fit, pad_color,
                       narrow=narrow, **({} if deliver_cube is None else {"lut": deliver_cube}), **({} if weave is None else {"interlace": weave}))
     pin_out = [torch.empty(end.shape(end.frames(B)), dtype=torch.uint8).pin_memory() for _ in range(NS)]    # what is downloaded and handed to the writer
@@ -449,7 +478,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                 sources.pop(next(iter(sources)))
             fmt, hw = (in_pix_fmt, yuv_hw) if key == YUV else ("rgb24", key)
             src = SourceEnd(dev, (h, w), fmt, in_matrix, in_range, in_chroma, hw, in_filter, crop, pix, widen=widen, deinterlace=deint,
-                            **({} if in_cube is None else {"lut": in_cube})).slots(Bs, NS)
+                            **({} if in_cube is None else {"lut": in_cube}), **({} if cable is None else {"signal": cable})).slots(Bs, NS)
             assert key != YUV or src.frame_bytes == yuv_bytes
         sources[key] = src
         return src
@@ -477,7 +506,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                 return a, (int(a.shape[0]), int(a.shape[1]))
             from PIL import Image
             a = np.asarray(Image.fromarray(np.ascontiguousarray(a, dtype=np.uint8)).resize((w, h), getattr(Image, in_filter.upper())))
-        return a, ((h, w) if widen or deint is not None or in_cube is not None else None)      # a half chain, a deinterlaced source, an in_lut: no direct upload, the frame goes through a source end
+        return a, ((h, w) if widen or deint is not None or in_cube is not None or cable is not None else None)      # a half chain, a deinterlaced source, an in_lut, an in_signal: no direct upload, the frame goes through a source end
 
     def drain(p):
         nonlocal written
@@ -530,6 +559,8 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                 if key != last_key and src is not direct:
                     src.restart()                    # deinterlace="adaptive": the frame before this batch's first is not its previous frame
                 last_key = key
+                if cable is not None:
+                    src.index = index // ratio       # the batch's first SOURCE frame in the stream: the Signal's t
                 src.convert(d, n, dev_in[d][:m])                                     # on the compute stream; nothing for `direct`
                 if down_done[d] is not None:
                     compute.wait_event(down_done[d])
