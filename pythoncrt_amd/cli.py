@@ -154,7 +154,7 @@ import os
 import sys
 import time
 
-from . import formats, sited, tables
+from . import formats, tables
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -272,19 +272,6 @@ def add_output_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     return p
 
 
-def interlace_from_args(a, deliver=None):
-    """(order, lowpass) of --deliver-interlace / --deliver-lowpass, or None for a progressive delivery.  `deliver` is deliver_size_from_args(a)."""
-    order, lowpass = getattr(a, "deliver_interlace", "off"), getattr(a, "deliver_lowpass", "none")
-    if order == "off":
-        if lowpass != "none":
-            raise SystemExit(f"--deliver-lowpass {lowpass} without --deliver-interlace tff | bff: there is nothing to filter")
-        return None
-    rows = deliver[0] if deliver is not None else int(a.height)
-    if 0 < rows < 2:
-        raise SystemExit(f"--deliver-interlace {order} with a delivery height of {rows}: a frame of one row has no two fields")
-    return order, lowpass
-
-
 def luts_from_args(a):
     """(in cube | None, delivery cube | None) of --in-lut / --deliver-lut, read once per parsed command line."""
     if getattr(a, "_luts", None) is None:
@@ -335,21 +322,6 @@ def in_crop_from_args(a):
         raise SystemExit(f"--in-crop-x {x} --in-crop-y {y} --in-crop-width {cw} --in-crop-height {ch}: the window leaves the "
                          f"--width {a.width} x --height {a.height} input")
     return y, x, ch, cw
-
-
-def check_fit_flags(a, deliver) -> None:
-    """--deliver-fit other than stretch needs a delivery size of its own to fit to (`deliver` is deliver_size_from_args(a))."""
-    pad_color_from_args(a)
-    if getattr(a, "deliver_fit", "stretch") != "stretch" and deliver is None:
-        raise SystemExit(f"--deliver-fit {a.deliver_fit} without --deliver-width / --deliver-height other than the render size: "
-                         "there is nothing to fit")
-
-
-def check_filter_flags(a, deliver) -> None:
-    """--deliver-filter other than bilinear needs a delivery resize to apply to (`deliver` is deliver_size_from_args(a))."""
-    if getattr(a, "deliver_filter", "bilinear") != "bilinear" and deliver is None:
-        raise SystemExit(f"--deliver-filter {a.deliver_filter} without --deliver-width / --deliver-height other than the render size: "
-                         "there is no delivery resize to filter")
 
 
 def add_input_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
@@ -404,26 +376,6 @@ def add_input_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     return p
 
 
-def signal_from_args(a):
-    """(signal, chroma, crawl) of --in-signal / --signal-chroma / --signal-crawl, or None for an input that came without a cable."""
-    signal, chroma, crawl = getattr(a, "in_signal", "rgb"), getattr(a, "signal_chroma", "sharp"), getattr(a, "signal_crawl", "on")
-    if signal == "rgb":
-        if chroma != "sharp" or crawl != "on":
-            raise SystemExit(f"--signal-chroma {chroma} / --signal-crawl {crawl} without --in-signal composite | svideo: there is no signal to decode")
-        return None
-    return signal, chroma, crawl == "on"
-
-
-def deinterlace_from_args(a):
-    """(method, order, fields) of --deinterlace / --field-order / --deinterlace-fields, or None for a progressive input."""
-    method, order, fields = getattr(a, "deinterlace", "off"), getattr(a, "field_order", "tff"), getattr(a, "deinterlace_fields", "first")
-    if method == "off":
-        if order != "tff" or fields != "first":
-            raise SystemExit(f"--field-order {order} / --deinterlace-fields {fields} without --deinterlace linear | edge | adaptive: there is nothing to deinterlace")
-        return None
-    return method, order, fields
-
-
 def settings_from_args(a):
     """The clamps of main() (ref:1225-1266) -> RenderSettings."""
     from .pipeline import RenderSettings
@@ -460,7 +412,7 @@ def settings_from_args(a):
     )
 
 
-def main_sharded(a, rank: int, world: int) -> int:
+def main_sharded(a, spec, rank: int, world: int) -> int:
     """One process per GPU (launched with `python -m torch.distributed.run --nproc-per-node N -m pythoncrt_amd.cli ...`):
     the clip's chunks of --batch frames are dealt round-robin over the ranks, each rank reads its chunks
     from the raw input file and writes them at the same offsets of the output file; with --persistence > 0 one
@@ -473,10 +425,10 @@ def main_sharded(a, rank: int, world: int) -> int:
         raise SystemExit("--deliver-width / --deliver-height are not supported by the sharded CLI (one process per GPU writes rgb24 at render size); "
                          "run one process, or scale behind it")
     for flag, on in (("--in-crop-x / --in-crop-y / --in-crop-width / --in-crop-height", any(getattr(a, "in_crop_" + k, 0) for k in ("x", "y", "width", "height"))),
-                     ("--deinterlace / --field-order / --deinterlace-fields", deinterlace_from_args(a) is not None),
-                     ("--in-signal / --signal-chroma / --signal-crawl", signal_from_args(a) is not None),
+                     ("--deinterlace / --field-order / --deinterlace-fields", spec.deinterlace is not None),
+                     ("--in-signal / --signal-chroma / --signal-crawl", spec.signal is not None),
                      ("--in-lut", bool(getattr(a, "in_lut", ""))), ("--deliver-lut", bool(getattr(a, "deliver_lut", ""))),
-                     ("--deliver-interlace / --deliver-lowpass", interlace_from_args(a) is not None),
+                     ("--deliver-interlace / --deliver-lowpass", spec.weave is not None),
                      ("--deliver-fit", getattr(a, "deliver_fit", "stretch") != "stretch"),
                      ("--deliver-pad-color", str(getattr(a, "deliver_pad_color", "0,0,0")) != "0,0,0")):
         if on:
@@ -621,45 +573,34 @@ def main_sharded(a, rank: int, world: int) -> int:
 
 
 def check_flags(a):
-    """Every refusal from the flags alone, before torch, a device or the output file.  -> delivery size | None, half chain (10-bit formats on
-    both ends, or --chain-pix half)?, (rank, world) | None."""
-    if a.in_chroma != "replicate" and a.in_pix_fmt not in sited.LAYOUTS:
-        raise SystemExit(f"--in-chroma {a.in_chroma} with --in-pix-fmt {a.in_pix_fmt}: only a 4:2:0 or 4:2:2 input has sub-sampled chroma to interpolate "
-                         f"({', '.join(sited.LAYOUTS)})")
-    if a.out_chroma != "center" and a.out_pix_fmt not in sited.LAYOUTS:
-        raise SystemExit(f"--out-chroma {a.out_chroma} with --out-pix-fmt {a.out_pix_fmt}: only a 4:2:0 or 4:2:2 output has chroma to down-sample "
-                         f"({', '.join(sited.LAYOUTS)})")
-    half = getattr(a, "chain_pix", "auto") == "half"
-    deep, deep_out = formats.bits(a.in_pix_fmt) == 10, formats.bits(a.out_pix_fmt) == 10
-    if getattr(a, "dither", "none") != "none" and (not half or deep_out):
-        raise SystemExit(f"--dither {a.dither} with --chain-pix {getattr(a, 'chain_pix', 'auto')} and --out-pix-fmt {a.out_pix_fmt}: only half frames "
-                         "narrowed to an 8-bit output are dithered; pass --chain-pix half and an 8-bit or rgb24 --out-pix-fmt")
-    deint = deinterlace_from_args(a)
-    signal_from_args(a)
-    deliver = deliver_size_from_args(a)
-    interlace_from_args(a, deliver)
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("CRTFX_FORCE_DIST") == "1":
-        if a.gui or not a.input or a.width <= 0 or a.height <= 0:
-            raise SystemExit("pass --input, --width and --height")
-        return deliver, None, (int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")))
-    check_filter_flags(a, deliver)
-    check_fit_flags(a, deliver)
-    if a.gui or not a.input:
-        raise SystemExit("the GUI is not part of this path; pass --input (raw rgb24 / yuv420p / nv12 / yuv422p / yuyv422 / uyvy422 / yuv420p10le / p010le / yuv444p10le / gbrp10le / x2rgb10le file or '-')")
-    if a.width <= 0 or a.height <= 0:
-        raise SystemExit("raw input needs --width and --height")
-    if deint is not None and a.height < 2:
-        raise SystemExit(f"--deinterlace {deint[0]} with --height {a.height}: a frame of one row has no two fields")
-    if not half and deep != deep_out:
-        raise SystemExit(f"--in-pix-fmt {a.in_pix_fmt} with --out-pix-fmt {a.out_pix_fmt}: a 10-bit format on one end only; the chain between them "
-                         "runs on half pixels or on uint8 ones — pass yuv420p10le / p010le (or yuv444p10le / gbrp10le / x2rgb10le) on both ends "
-                         "or on neither")
-    crop = in_crop_from_args(a)
-    if deep and crop is not None and crop[2:] != (int(a.height), int(a.width)):
-        raise SystemExit(f"--in-crop-width {crop[3]} --in-crop-height {crop[2]} differs from --width {a.width} x --height {a.height}: a 10-bit input "
-                         "cannot be resized (IngestResize has no half path)")
-    luts_from_args(a)                                              # an unreadable or malformed cube
-    return deliver, deep or half, None
+    """Every refusal from the flags alone, before torch, a device or the output file: options.RULES in their flag wording, around the parsers
+    of the CLI's own syntax.  -> the ChainOptions, (rank, world) | None.  For the sharded CLI only the rules in front of its branch have run:
+    it refuses a crop, a pad colour and a cube itself, and its spec holds none."""
+    from .options import ChainOptions, OptionError, Raw, refuse
+    hw = (a.height if a.height > 0 else None, a.width if a.width > 0 else None)        # None: not given (refused below, behind the sharded branch)
+    v = Raw(render_hw=hw, in_size=hw, resize_on="device", in_pix_fmt=a.in_pix_fmt, in_matrix=a.in_matrix, in_range=a.in_range, in_chroma=a.in_chroma,
+            in_filter=a.in_filter, in_crop=None, deinterlace=a.deinterlace, field_order=a.field_order, deinterlace_fields=a.deinterlace_fields,
+            in_signal=a.in_signal, signal_chroma=a.signal_chroma, signal_crawl=a.signal_crawl == "on", in_lut=None, chain_pix=a.chain_pix,
+            dither=a.dither, out_pix_fmt=a.out_pix_fmt, out_matrix=a.out_matrix, out_range=a.out_range, out_chroma=a.out_chroma,
+            deliver_size=deliver_size_from_args(a), deliver_filter=a.deliver_filter, deliver_fit=a.deliver_fit, deliver_pad_color=(0, 0, 0),
+            deliver_lut=None, deliver_interlace=a.deliver_interlace, deliver_lowpass=a.deliver_lowpass)
+    try:
+        refuse(v, "flags", early=True)
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("CRTFX_FORCE_DIST") == "1":
+            if a.gui or not a.input or a.width <= 0 or a.height <= 0:
+                raise SystemExit("pass --input, --width and --height")
+            return ChainOptions.build(v), (int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")))
+        v.deliver_pad_color = pad_color_from_args(a)
+        if a.gui or not a.input:
+            raise SystemExit("the GUI is not part of this path; pass --input (raw rgb24 / yuv420p / nv12 / yuv422p / yuyv422 / uyvy422 / yuv420p10le / p010le / yuv444p10le / gbrp10le / x2rgb10le file or '-')")
+        if a.width <= 0 or a.height <= 0:
+            raise SystemExit("raw input needs --width and --height")
+        v.in_crop = in_crop_from_args(a)
+        refuse(v, "flags", early=False)
+    except OptionError as e:
+        raise SystemExit(str(e)) from e
+    v.in_lut, v.deliver_lut = luts_from_args(a)                    # an unreadable or malformed cube
+    return ChainOptions.build(v), None
 
 
 def open_output(a, fin, out_path: str, B: int, in_bytes: int, out_bytes: int, ratio: int = 1, frames=None):
@@ -832,12 +773,11 @@ def staging_report(index: int, marks, waits, times, reader, writer, pipes) -> No
 
 def main(argv=None) -> int:
     a = add_input_flags(add_output_flags(build_parser())).parse_args(argv)
-    deliver, deep, ranks = check_flags(a)
+    spec, ranks = check_flags(a)
     if ranks is not None:
-        return main_sharded(a, *ranks)
+        return main_sharded(a, spec, *ranks)
     t_start = time.perf_counter()
     import torch
-    from .ends import DeliveryEnd, SourceEnd, depth_stages
     from .pipeline import FramePipeline
     from .staging import _Reader, _Writer
     from .text import make_text_overlay_rgba
@@ -850,28 +790,15 @@ def main(argv=None) -> int:
     dev = torch.device("cuda", torch.cuda.current_device())
     seed = a.noise_seed if a.noise_seed is not None else int.from_bytes(os.urandom(8), "little")
     overlay = make_text_overlay_rgba(w, h, a.text, a.text_font, a.text_size, a.text_color, (a.text_x, a.text_y)) if a.text else None   # ref:1076
-    pix = torch.float16 if deep else torch.uint8                   # 10-bit formats on both ends, or --chain-pix half: the chain runs on half pixels
-    # --chain-pix half: uint8 stages in front of the chain end in a Widen, a Narrow stands in front of the 8-bit egress plan (include/crtfx_depth.h)
-    _, widen, narrow = depth_stages(a.in_pix_fmt, a.out_pix_fmt, a.chain_pix, a.dither)
+    pix = torch.float16 if spec.half else torch.uint8              # 10-bit formats on both ends, or --chain-pix half: the chain runs on half pixels
     pipe = FramePipeline(dev, h, w, rs, fps=fps_out, noise_seed=seed, dtype=pix, text_overlay_rgba=overlay, text_overlay_after=bool(a.text_after))
     t_engine = time.perf_counter() - t_start - t_imports
     fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb", buffering=0)
     out_path = a.output if a.output else (a.input + "_crt.rgb" if a.input != "-" else "-")
-    B, NS = max(1, int(a.batch)), 3
-    deint = deinterlace_from_args(a)                               # an interlaced input: every format then has a source end, rgb24 too
-    ratio = 2 if deint is not None and deint[2] == "both" else 1    # delivery frames per input frame
-    weave = interlace_from_args(a, deliver)                        # an interlaced delivery: whole pairs per batch
-    if ratio == 2 or weave is not None:
-        B = max(2, B - B % 2)                                      # the chain's batch: both fields of B // 2 input frames
-    Bs = B // ratio                                                # input frames per batch
-    in_cube, deliver_cube = luts_from_args(a)                      # --in-lut: every format then has a source end, rgb24 too
-    end = DeliveryEnd(dev, (h, w), pix, a.out_pix_fmt, a.out_matrix, a.out_range, a.out_chroma, deliver, a.deliver_filter, a.deliver_fit, pad_color_from_args(a),
-                      narrow=narrow, **({} if deliver_cube is None else {"lut": deliver_cube}), **({} if weave is None else {"interlace": weave}))
-    crop = in_crop_from_args(a)                                    # a window of the input: an rgb24 input then has a source end too
-    cable = signal_from_args(a)                                    # --in-signal: every format then has a source end, rgb24 too
-    source = (SourceEnd(dev, (h, w), a.in_pix_fmt, a.in_matrix, a.in_range, a.in_chroma, (h, w), a.in_filter, crop, pix, widen=widen, deinterlace=deint,
-                        **({} if in_cube is None else {"lut": in_cube}), **({} if cable is None else {"signal": cable}))
-              if a.in_pix_fmt != "rgb24" or crop is not None or widen or deint is not None or in_cube is not None or cable is not None else None)    # half chain: an rgb24 input goes through a Widen
+    NS, ratio = 3, spec.ratio                                      # delivery frames per input frame
+    B, Bs = spec.batch(a.batch)                                    # the chain's batch, input frames per batch
+    end = spec.delivery_end(dev, pix)
+    source = None if spec.direct else spec.source_end(dev, (h, w), pix)      # every stage in front of the chain gives an rgb24 input a source end too
     in_bytes = h * w * 3 if source is None else source.frame_bytes
     t0 = time.perf_counter()
     fout, in_pos, out_pos, pipes, out_plan = open_output(a, fin, out_path, B, in_bytes, end.frame_bytes, ratio, end.frames)

@@ -21,7 +21,7 @@ from typing import Callable, Iterable, Optional, Tuple
 
 import numpy as np
 
-from . import formats, sited, tables
+from . import formats
 
 # process_video keywords that belong to its container / codec plumbing (out of scope): accepted so that a caller can forward its
 # own keyword dictionary unchanged, and ignored
@@ -310,122 +310,23 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     import os
     import torch
     from .pipeline import FramePipeline, RenderSettings
-    from .ends import DeliveryEnd, SourceEnd, StagingSlots, depth_stages
+    from .ends import StagingSlots
+    from .options import ChainOptions, Raw
     unknown = set(io_keywords) - set(_IO_KEYS)
     if unknown:
         raise TypeError(f"process_frames() got unexpected keyword arguments {sorted(unknown)}")
-    if resize_on not in ("device", "host"):
-        raise ValueError(f"resize_on must be 'device' or 'host', got {resize_on!r}")
-    if out_pix_fmt not in formats.PIX_FMTS:
-        raise ValueError("out_pix_fmt must be 'rgb24', 'yuv420p' or 'nv12', 'yuv422p', 'yuyv422' or 'uyvy422' (or, with a 10-bit input, "
-                         f"'yuv420p10le' or 'p010le', 'yuv444p10le', 'gbrp10le' or 'x2rgb10le'), got {out_pix_fmt!r}")
-    if in_pix_fmt not in formats.PIX_FMTS:
-        raise ValueError("in_pix_fmt must be 'rgb24', 'yuv420p' or 'nv12', 'yuv422p', 'yuyv422' or 'uyvy422' (or, with a 10-bit output, "
-                         f"'yuv420p10le' or 'p010le', 'yuv444p10le', 'gbrp10le' or 'x2rgb10le'), got {in_pix_fmt!r}")
-    if in_chroma not in ("replicate", "left", "center"):
-        raise ValueError(f"in_chroma must be 'replicate', 'left' or 'center', got {in_chroma!r}")
-    if in_chroma != "replicate" and in_pix_fmt not in sited.LAYOUTS:
-        raise ValueError(f"in_chroma={in_chroma!r} with in_pix_fmt={in_pix_fmt!r}: only a 4:2:0 or 4:2:2 input has sub-sampled chroma to "
-                         f"interpolate ({', '.join(sited.LAYOUTS)})")
-    if out_chroma not in ("center", "left"):
-        raise ValueError(f"out_chroma must be 'center' or 'left', got {out_chroma!r}")
-    if out_chroma != "center" and out_pix_fmt not in sited.LAYOUTS:
-        raise ValueError(f"out_chroma={out_chroma!r} with out_pix_fmt={out_pix_fmt!r}: only a 4:2:0 or 4:2:2 output has chroma to "
-                         f"down-sample ({', '.join(sited.LAYOUTS)})")
-    crop = parse_in_crop(in_crop, None if in_pix_fmt == "rgb24" else ((int(out_h), int(out_w)) if in_size is None else (int(in_size[0]), int(in_size[1]))))
-    if crop is not None and resize_on == "host":
-        raise ValueError(f"resize_on='host' cannot be combined with in_crop={crop}: the window is cut on the device")
-    if deliver_fit not in DELIVER_FITS:
-        raise ValueError(f"deliver_fit must be one of {', '.join(DELIVER_FITS)}, got {deliver_fit!r}")
-    pad_color = parse_pad_color(deliver_pad_color)
-    from .depth import DITHERS
-    if chain_pix not in CHAIN_PIX:
-        raise ValueError(f"chain_pix must be one of {', '.join(CHAIN_PIX)}, got {chain_pix!r} (dither={dither!r})")
-    if dither not in DITHERS:
-        raise ValueError(f"dither must be one of {', '.join(DITHERS)}, got {dither!r} (chain_pix={chain_pix!r})")
-    from .adeint import METHOD as ADAPTIVE
-    from .deint import FIELDS, ORDERS
-    from .deint import METHODS as SPATIAL
-    METHODS = SPATIAL + (ADAPTIVE,)
-    if deinterlace != "off" and deinterlace not in METHODS:
-        raise ValueError(f"deinterlace must be 'off' or one of {', '.join(METHODS)}, got {deinterlace!r}")
-    if field_order not in ORDERS:
-        raise ValueError(f"field_order must be one of {', '.join(ORDERS)}, got {field_order!r}")
-    if deinterlace_fields not in FIELDS:
-        raise ValueError(f"deinterlace_fields must be one of {', '.join(FIELDS)}, got {deinterlace_fields!r}")
-    if deinterlace == "off" and (field_order != "tff" or deinterlace_fields != "first"):
-        raise ValueError(f"field_order={field_order!r} / deinterlace_fields={deinterlace_fields!r} with deinterlace='off': there is nothing to "
-                         "deinterlace")
-    if deinterlace != "off":
-        if resize_on == "host":
-            raise ValueError(f"resize_on='host' cannot be combined with deinterlace={deinterlace!r}: the fields are separated on the device, in "
-                             "front of the resize")
-        src_h = int(in_size[0]) if in_size is not None else (int(out_h) if in_pix_fmt != "rgb24" else None)
-        if src_h is not None and src_h < 2:
-            raise ValueError(f"deinterlace={deinterlace!r}: a source frame of {src_h} row(s) has no two fields")
-    deint = None if deinterlace == "off" else (deinterlace, field_order, deinterlace_fields)
-    ratio = 2 if deint is not None and deinterlace_fields == "both" else 1      # frames written per source frame
-    half = chain_pix == "half"
-    deep, deep_out = formats.bits(in_pix_fmt) == 10, formats.bits(out_pix_fmt) == 10       # under "auto": both ends or neither
-    if dither != "none" and (not half or deep_out):
-        raise ValueError(f"dither={dither!r} with chain_pix={chain_pix!r} and out_pix_fmt={out_pix_fmt!r}: only half frames narrowed to an 8-bit "
-                         "delivery are dithered (chain_pix='half' and an 8-bit or rgb24 out_pix_fmt)")
-    if not half and deep != deep_out:
-        raise ValueError(f"in_pix_fmt={in_pix_fmt!r} with out_pix_fmt={out_pix_fmt!r}: a 10-bit format on one end only — the chain between "
-                         "them runs on half pixels or on uint8 ones, and the 8-bit stages have no half path (the 10-bit ones no uint8 path)")
-    if deep and crop is not None and crop[2:] != (int(out_h), int(out_w)):
-        raise ValueError(f"in_crop={crop} leaves a {crop[2]} x {crop[3]} window that differs from the output size {(int(out_h), int(out_w))}: a "
-                         "10-bit input cannot be resized (IngestResize has no half path)")
-    if deep and crop is None and in_size is not None and (int(in_size[0]), int(in_size[1])) != (int(out_h), int(out_w)):
-        raise ValueError(f"in_size={tuple(in_size)} differs from the output size {(int(out_h), int(out_w))}: a 10-bit input cannot be "
-                         "resized (IngestResize has no half path)")
-    if in_pix_fmt != "rgb24" and resize_on == "host":
-        raise ValueError(f"resize_on='host' cannot be combined with in_pix_fmt={in_pix_fmt!r}: there is no host RGB frame to hand to Pillow")
-    deliver = parse_deliver_size(deliver_size, int(out_h), int(out_w))         # None: delivered as rendered
-    for name, value in (("in_filter", in_filter), ("deliver_filter", deliver_filter)):
-        if value not in tables.RESAMPLE_FILTERS:
-            raise ValueError(f"{name} must be one of {', '.join(tables.RESAMPLE_FILTERS)}, got {value!r}")
-    if deliver_filter != "bilinear" and deliver is None:
-        raise ValueError(f"deliver_filter={deliver_filter!r} without a deliver_size that differs from the render size: there is no delivery "
-                         "resize to filter")
-    if deliver_fit != "stretch" and deliver is None:
-        raise ValueError(f"deliver_fit={deliver_fit!r} without a deliver_size that differs from the render size: there is nothing to fit")
-    from .interlace import LOWPASS
-    from .interlace import ORDERS as WEAVE_ORDERS
-    if deliver_interlace != "off" and deliver_interlace not in WEAVE_ORDERS:
-        raise ValueError(f"deliver_interlace must be 'off' or one of {', '.join(WEAVE_ORDERS)}, got {deliver_interlace!r}")
-    if deliver_lowpass not in LOWPASS:
-        raise ValueError(f"deliver_lowpass must be one of {', '.join(LOWPASS)}, got {deliver_lowpass!r}")
-    if deliver_interlace == "off" and deliver_lowpass != "none":
-        raise ValueError(f"deliver_lowpass={deliver_lowpass!r} with deliver_interlace='off': there is nothing to filter")
-    weave = None if deliver_interlace == "off" else (deliver_interlace, deliver_lowpass)
-    if weave is not None and (deliver or (int(out_h), int(out_w)))[0] < 2:
-        raise ValueError(f"deliver_interlace={deliver_interlace!r}: a delivered frame of {(deliver or (int(out_h), int(out_w)))[0]} row(s) has no two fields")
-    from .signal import CHROMAS, SIGNALS
-    if not isinstance(in_signal, str) or (in_signal != "rgb" and in_signal not in SIGNALS):
-        raise ValueError(f"in_signal must be 'rgb' or one of {', '.join(SIGNALS)}, got {in_signal!r}")
-    if not isinstance(signal_chroma, str) or signal_chroma not in CHROMAS:
-        raise ValueError(f"signal_chroma must be one of {', '.join(CHROMAS)}, got {signal_chroma!r}")
-    if not isinstance(signal_crawl, bool):
-        raise ValueError(f"signal_crawl must be True or False, got {signal_crawl!r}")
-    if in_signal == "rgb" and (signal_chroma != "sharp" or not signal_crawl):
-        raise ValueError(f"signal_chroma={signal_chroma!r} / signal_crawl={signal_crawl!r} with in_signal='rgb': there is no signal to decode")
-    if in_signal != "rgb" and resize_on == "host":
-        raise ValueError(f"resize_on='host' cannot be combined with in_signal={in_signal!r}: the signal is formed on the device, at the source's size, "
-                         "in front of the device's resize")
-    cable = None if in_signal == "rgb" else (in_signal, signal_chroma, signal_crawl)
-    from .cube import as_cube
-    if in_lut is not None and resize_on == "host":
-        raise ValueError("resize_on='host' cannot be combined with in_lut: the cube is applied on the device, behind the device's resize")
-    in_cube = as_cube(in_lut, "in_lut") if in_lut is not None else None
-    deliver_cube = as_cube(deliver_lut, "deliver_lut") if deliver_lut is not None else None
+    spec = ChainOptions.build(Raw(                                             # every refusal: options.RULES
+        render_hw=(int(out_h), int(out_w)), resize_on=resize_on, out_pix_fmt=out_pix_fmt, out_matrix=out_matrix, out_range=out_range,
+        in_pix_fmt=in_pix_fmt, in_matrix=in_matrix, in_range=in_range, in_size=in_size, in_chroma=in_chroma, out_chroma=out_chroma,
+        deliver_size=deliver_size, in_filter=in_filter, deliver_filter=deliver_filter, in_crop=in_crop, deliver_fit=deliver_fit,
+        deliver_pad_color=deliver_pad_color, chain_pix=chain_pix, dither=dither, deinterlace=deinterlace, field_order=field_order,
+        deinterlace_fields=deinterlace_fields, in_lut=in_lut, deliver_lut=deliver_lut, deliver_interlace=deliver_interlace,
+        deliver_lowpass=deliver_lowpass, in_signal=in_signal, signal_chroma=signal_chroma, signal_crawl=signal_crawl), "keywords")
+    crop, ratio, deep = spec.crop, spec.ratio, formats.bits(in_pix_fmt) == 10
     if not torch.cuda.is_available():
         raise RuntimeError("no ROCm device visible; pythoncrt_amd has no CPU fallback")
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    h, w, B = int(out_h), int(out_w), max(1, int(batch))
-    if ratio == 2 or weave is not None:
-        B = max(2, B - B % 2)                                                  # the chain's batch: both fields of B // 2 source frames, whole pairs for the Interlace
-    Bs = B // ratio                                                            # source frames per batch
+    (h, w), (B, Bs) = spec.render_hw, spec.batch(batch)                        # the chain's batch, source frames per batch
     rs = RenderSettings(
         scanline_strength=float(scanline_strength), triad_strength=float(triad_strength), triad_gamma=float(triad_gamma),
         triad_preserve_luma=bool(triad_preserve_luma), triad_softness=float(triad_softness), aberration_px=int(aberration_px),
@@ -441,15 +342,13 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         from .text import make_text_overlay_rgba
         overlay = make_text_overlay_rgba(w, h, text, text_font, int(text_size), text_color, tuple(text_pos))
     seed = int(noise_seed) if noise_seed is not None else int.from_bytes(os.urandom(8), "little")
-    on_half, widen, narrow = depth_stages(in_pix_fmt, out_pix_fmt, chain_pix, dither)      # widen: uint8 stages in front of a half chain end in a Widen
-    pix = torch.float16 if on_half else torch.uint8                            # what the chain runs on
+    pix = torch.float16 if spec.half else torch.uint8                          # what the chain runs on
     pipe = FramePipeline(dev, h, w, rs, fps=float(fps_out), noise_seed=seed, dtype=pix, text_overlay_rgba=overlay, text_overlay_after=bool(text_after))
     total = max(1, int(total_frames)) if total_frames else None
 
     NS = 2
-    pin_in = [torch.empty((B, h, w, 3), dtype=torch.uint8).pin_memory() for _ in range(NS)] if in_pix_fmt == "rgb24" and not widen and deint is None and in_cube is None and cable is None else None   # else: a SourceEnd's own
-    end = DeliveryEnd(dev, (h, w), pix, out_pix_fmt, out_matrix, out_range, out_chroma, deliver, deliver_filter, deliver_fit, pad_color,
-                      narrow=narrow, **({} if deliver_cube is None else {"lut": deliver_cube}), **({} if weave is None else {"interlace": weave}))
+    pin_in = [torch.empty((B, h, w, 3), dtype=torch.uint8).pin_memory() for _ in range(NS)] if spec.direct else None   # else: a SourceEnd's own
+    end = spec.delivery_end(dev, pix)
     pin_out = [torch.empty(end.shape(end.frames(B)), dtype=torch.uint8).pin_memory() for _ in range(NS)]    # what is downloaded and handed to the writer
     dev_in = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]
     dev_out = [torch.empty((B, h, w, 3), dtype=pix, device=dev) for _ in range(NS)]
@@ -467,7 +366,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     last_key = None                  # the source key of the batch before: where it changes, a source that keeps a history starts a new one
     carry = None                     # a frame already taken from the iterator that starts the next batch (its source size differs)
     YUV = "yuv"                      # the key of the one 4:2:0 / 4:2:2 source (its size is fixed by in_size): a SourceEnd
-    yuv_hw = (h, w) if in_size is None else (int(in_size[0]), int(in_size[1]))
+    yuv_hw = spec.in_size or (h, w)
     yuv_bytes = formats.frame_bytes(yuv_hw[0], yuv_hw[1], in_pix_fmt)
 
     def source(key):
@@ -476,9 +375,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
             if len(sources) >= MAX_SOURCES:      # rare: drop the least recently used size once its queued work is done
                 torch.cuda.synchronize(dev)
                 sources.pop(next(iter(sources)))
-            fmt, hw = (in_pix_fmt, yuv_hw) if key == YUV else ("rgb24", key)
-            src = SourceEnd(dev, (h, w), fmt, in_matrix, in_range, in_chroma, hw, in_filter, crop, pix, widen=widen, deinterlace=deint,
-                            **({} if in_cube is None else {"lut": in_cube}), **({} if cable is None else {"signal": cable})).slots(Bs, NS)
+            src = spec.source_end(dev, yuv_hw if key == YUV else key, pix).slots(Bs, NS)
             assert key != YUV or src.frame_bytes == yuv_bytes
         sources[key] = src
         return src
@@ -495,7 +392,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
             return a, YUV
         if a.ndim != 3 or a.shape[2] != 3:
             raise ValueError(f"frames must be H x W x 3 RGB arrays, got {a.shape}")
-        if deint is not None and a.shape[0] < 2:
+        if spec.deinterlace is not None and a.shape[0] < 2:
             raise ValueError(f"deinterlace={deinterlace!r}: a frame of {a.shape[0]} x {a.shape[1]} has no two fields")
         if crop is not None:                                                    # every frame goes through a SourceEnd of ITS size
             if a.shape[0] < crop[0] + crop[2] or a.shape[1] < crop[1] + crop[3]:
@@ -506,7 +403,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                 return a, (int(a.shape[0]), int(a.shape[1]))
             from PIL import Image
             a = np.asarray(Image.fromarray(np.ascontiguousarray(a, dtype=np.uint8)).resize((w, h), getattr(Image, in_filter.upper())))
-        return a, ((h, w) if widen or deint is not None or in_cube is not None or cable is not None else None)      # a half chain, a deinterlaced source, an in_lut, an in_signal: no direct upload, the frame goes through a source end
+        return a, (None if spec.direct else (h, w))      # a half chain, a deinterlaced source, an in_lut, an in_signal: no direct upload, the frame goes through a source end
 
     def drain(p):
         nonlocal written
@@ -559,7 +456,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                 if key != last_key and src is not direct:
                     src.restart()                    # deinterlace="adaptive": the frame before this batch's first is not its previous frame
                 last_key = key
-                if cable is not None:
+                if spec.signal is not None:
                     src.index = index // ratio       # the batch's first SOURCE frame in the stream: the Signal's t
                 src.convert(d, n, dev_in[d][:m])                                     # on the compute stream; nothing for `direct`
                 if down_done[d] is not None:

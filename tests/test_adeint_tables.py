@@ -389,9 +389,11 @@ def test_cli_refusals_and_the_sharded_cli(tmp_path, monkeypatch):
     refused(["--field-order", "bff"], "nothing to deinterlace", "adaptive")
     parse = cli.add_input_flags(cli.add_output_flags(cli.build_parser())).parse_args
     a = parse(base + ["--deinterlace", "adaptive"])
-    assert cli.deinterlace_from_args(a) == ("adaptive", "tff", "first") and cli.check_flags(a) == (None, False, None)
+    spec, ranks = cli.check_flags(a)
+    assert spec.deinterlace == ("adaptive", "tff", "first") and spec.deliver is None and spec.half is False and ranks is None
     a = parse(base + ["--deinterlace", "adaptive", "--field-order", "bff", "--deinterlace-fields", "both"])
-    assert cli.deinterlace_from_args(a) == ("adaptive", "bff", "both") and cli.check_flags(a) == (None, False, None)
+    spec, ranks = cli.check_flags(a)
+    assert spec.deinterlace == ("adaptive", "bff", "both") and spec.deliver is None and spec.half is False and ranks is None
     assert "--deinterlace adaptive" in cli.__doc__ and "crtfx_adeint.h" in cli.__doc__
     monkeypatch.setenv("CRTFX_FORCE_DIST", "1")
     refused(["--deinterlace", "adaptive"], "sharded CLI", "--deinterlace")

@@ -334,10 +334,12 @@ def test_cli_refusals_and_the_sharded_cli(tmp_path, monkeypatch):
     assert not any(act.dest in ("deinterlace", "field_order", "deinterlace_fields") for act in cli.add_output_flags(cli.build_parser())._actions)
     parse = cli.add_input_flags(cli.add_output_flags(cli.build_parser())).parse_args
     a = parse(base)
-    assert (a.deinterlace, a.field_order, a.deinterlace_fields) == ("off", "tff", "first") and cli.deinterlace_from_args(a) is None
-    assert cli.check_flags(a) == (None, False, None)
+    spec, ranks = cli.check_flags(a)
+    assert (a.deinterlace, a.field_order, a.deinterlace_fields) == ("off", "tff", "first") and spec.deinterlace is None
+    assert spec.deliver is None and spec.half is False and ranks is None
     a = parse(base + ["--deinterlace", "edge", "--field-order", "bff", "--deinterlace-fields", "both"])
-    assert cli.deinterlace_from_args(a) == ("edge", "bff", "both") and cli.check_flags(a) == (None, False, None)
+    spec, ranks = cli.check_flags(a)
+    assert spec.deinterlace == ("edge", "bff", "both") and spec.deliver is None and spec.half is False and ranks is None
     assert "--deinterlace edge" in cli.__doc__ and "uyvy422" in cli.__doc__ and "--fps 60" in cli.__doc__
     monkeypatch.setenv("CRTFX_FORCE_DIST", "1")
     refused(["--deinterlace", "linear"], "sharded CLI", "--deinterlace")

@@ -307,9 +307,11 @@ def test_cli_flags_refusals_and_the_sharded_cli(tmp_path, monkeypatch):
     assert (a.chain_pix, a.dither) == ("auto", "none")
     a = cli.add_input_flags(cli.add_output_flags(cli.build_parser())).parse_args(base + ["--chain-pix", "half", "--dither", "ordered", "--in-pix-fmt", "p010le"])
     assert (a.chain_pix, a.dither) == ("half", "ordered")
-    assert cli.check_flags(a) == (None, True, None)                             # admitted: delivered as rendered, a half chain, one process
+    spec, ranks = cli.check_flags(a)
+    assert spec.deliver is None and spec.half is True and ranks is None        # admitted: delivered as rendered, a half chain, one process
     a = cli.add_input_flags(cli.add_output_flags(cli.build_parser())).parse_args(base)
-    assert cli.check_flags(a) == (None, False, None)
+    spec, ranks = cli.check_flags(a)
+    assert spec.deliver is None and spec.half is False and ranks is None
     monkeypatch.setenv("CRTFX_FORCE_DIST", "1")
     refused(["--chain-pix", "half"], "sharded CLI", "--chain-pix half", "--dither")
     refused(["--chain-pix", "half", "--dither", "ordered"], "sharded CLI", "--chain-pix half", "--dither")

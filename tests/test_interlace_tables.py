@@ -441,12 +441,15 @@ def test_cli_refusals_and_the_sharded_cli(tmp_path, monkeypatch):
     assert sum(act.dest in ("deliver_interlace", "deliver_lowpass") for act in cli.add_output_flags(cli.build_parser())._actions) == 2
     parse = cli.add_input_flags(cli.add_output_flags(cli.build_parser())).parse_args
     a = parse(base)
-    assert (a.deliver_interlace, a.deliver_lowpass) == ("off", "none") and cli.interlace_from_args(a) is None
-    assert cli.check_flags(a) == (None, False, None)
+    spec, ranks = cli.check_flags(a)
+    assert (a.deliver_interlace, a.deliver_lowpass) == ("off", "none") and spec.weave is None
+    assert spec.deliver is None and spec.half is False and ranks is None
     a = parse(base + ["--deliver-interlace", "bff", "--deliver-lowpass", "complex"])
-    assert cli.interlace_from_args(a) == ("bff", "complex") and cli.check_flags(a) == (None, False, None)
+    spec, ranks = cli.check_flags(a)
+    assert spec.weave == ("bff", "complex") and spec.deliver is None and spec.half is False and ranks is None
     a = parse(one_row + ["--deliver-interlace", "tff", "--deliver-width", "80", "--deliver-height", "2"])
-    assert cli.interlace_from_args(a, cli.deliver_size_from_args(a)) == ("tff", "none")
+    spec, ranks = cli.check_flags(a)
+    assert spec.weave == ("tff", "none")
     assert "--deliver-interlace bff --deliver-lowpass linear" in cli.__doc__ and "+ilme+ildct" in cli.__doc__
     monkeypatch.setenv("CRTFX_FORCE_DIST", "1")
     refused(["--deliver-interlace", "tff"], "--deliver-interlace / --deliver-lowpass is not supported by the sharded CLI")

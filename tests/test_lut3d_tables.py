@@ -480,9 +480,11 @@ def test_cli_flags_refusals_and_the_sharded_cli(tmp_path, monkeypatch):
     assert not any(act.dest in ("in_lut", "deliver_lut") for act in cli.build_parser()._actions)
     a = cli.add_input_flags(cli.add_output_flags(cli.build_parser())).parse_args(base)
     assert (a.in_lut, a.deliver_lut) == ("", "") and cli.luts_from_args(a) == (None, None)
-    assert cli.check_flags(a) == (None, False, None)
+    spec, ranks = cli.check_flags(a)
+    assert spec.deliver is None and spec.half is False and ranks is None
     a = cli.add_input_flags(cli.add_output_flags(cli.build_parser())).parse_args(base + ["--in-lut", good, "--deliver-lut", good])
-    assert cli.check_flags(a) == (None, False, None)
+    spec, ranks = cli.check_flags(a)
+    assert spec.deliver is None and spec.half is False and ranks is None
     cubes = cli.luts_from_args(a)
     assert [c.size for c in cubes] == [2, 2] and cli.luts_from_args(a) is cubes      # read once
     monkeypatch.setenv("CRTFX_FORCE_DIST", "1")

@@ -548,12 +548,15 @@ def test_cli_refusals_and_the_sharded_cli(tmp_path, monkeypatch):
     assert sum(act.dest in dests for act in cli.add_input_flags(cli.build_parser())._actions) == 3
     parse = cli.add_input_flags(cli.add_output_flags(cli.build_parser())).parse_args
     a = parse(base)
-    assert (a.in_signal, a.signal_chroma, a.signal_crawl) == ("rgb", "sharp", "on") and cli.signal_from_args(a) is None
-    assert cli.check_flags(a) == (None, False, None)
+    spec, ranks = cli.check_flags(a)
+    assert (a.in_signal, a.signal_chroma, a.signal_crawl) == ("rgb", "sharp", "on") and spec.signal is None
+    assert spec.deliver is None and spec.half is False and ranks is None
     a = parse(base + ["--in-signal", "composite"])
-    assert cli.signal_from_args(a) == ("composite", "sharp", True) and cli.check_flags(a) == (None, False, None)
+    spec, ranks = cli.check_flags(a)
+    assert spec.signal == ("composite", "sharp", True) and spec.deliver is None and spec.half is False and ranks is None
     a = parse(base + ["--in-signal", "svideo", "--signal-chroma", "soft", "--signal-crawl", "off"])
-    assert cli.signal_from_args(a) == ("svideo", "soft", False)
+    spec, ranks = cli.check_flags(a)
+    assert spec.signal == ("svideo", "soft", False)
     doc = " ".join(cli.__doc__.split())
     assert "--in-signal composite --signal-chroma soft" in doc and "four times the colour subcarrier" in doc and "SD-width" in doc
     monkeypatch.setenv("CRTFX_FORCE_DIST", "1")
