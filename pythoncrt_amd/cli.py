@@ -54,6 +54,11 @@ With a 4:2:0 / 4:2:2 `--in-pix-fmt`, `--in-chroma left` (MPEG-2 / H.264 / HEVC s
 `--in-chroma center` (JPEG-family sources) interpolates chroma at its siting on the GPU instead of replicating each sample over its pixels
 (UnpackSited, include/crtfx_sited.h); the default `replicate` is the path as it was.
 
+With a 4:2:0 `--in-pix-fmt` from an interlaced encoder (DVD, 480i / 576i / 1080i broadcast), `--in-chroma-rows interlaced` takes chroma rows
+0, 2, 4, ... as the top field's and 1, 3, 5, ... as the bottom field's, so that every luma row gets the colour of its own field
+(UnpackField420, include/crtfx_field420.h) and `--deinterlace` reads fields whose colour is their own; the default `progressive` is the
+path as it was.
+
 With a 4:2:0 / 4:2:2 `--out-pix-fmt`, `--out-chroma left` filters every chroma sample onto its first luma column on the GPU
 (EgressSited, include/crtfx_egress_sited.h) — the siting ffmpeg's muxers tag or assume for such a file, what ffprobe then reports as
 chroma_location=left (or nothing) and the only siting 4:2:2 defines; pass `-chroma_sample_location left` to the encoder.  The default
@@ -337,6 +342,10 @@ def add_input_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--in-chroma", type=str, default="replicate", choices=["replicate", "left", "center"],
                    help="4:2:0 / 4:2:2 input: replicate each chroma sample over its pixels (default), or interpolate chroma at its siting on the GPU: "
                         "left (MPEG-2 / H.264 / HEVC; ffprobe's chroma_location=left or nothing) or center (JPEG-family sources)")
+    p.add_argument("--in-chroma-rows", type=str, default="progressive", choices=["progressive", "interlaced"],
+                   help="yuv420p / nv12 / yuv420p10le / p010le input: progressive (default) pairs chroma row c with luma rows 2c and 2c + 1; interlaced reads "
+                        "what an interlaced encoder wrote (DVD, 480i / 576i / 1080i broadcast): chroma rows alternate between the fields and every luma "
+                        "row takes colour from rows of its own field on the GPU (include/crtfx_field420.h), at --in-chroma; pass it with --deinterlace")
     p.add_argument("--in-filter", type=str, default="bilinear", choices=list(tables.RESAMPLE_FILTERS),
                    help="filter of the resize that brings a source of another size to --width x --height (process_frames(in_filter=)): Pillow's "
                         "BILINEAR (default) or another of its five; a raw input file is read at --width x --height, so nothing is resized in "
@@ -583,7 +592,7 @@ def check_flags(a):
             in_signal=a.in_signal, signal_chroma=a.signal_chroma, signal_crawl=a.signal_crawl == "on", in_lut=None, chain_pix=a.chain_pix,
             dither=a.dither, out_pix_fmt=a.out_pix_fmt, out_matrix=a.out_matrix, out_range=a.out_range, out_chroma=a.out_chroma,
             deliver_size=deliver_size_from_args(a), deliver_filter=a.deliver_filter, deliver_fit=a.deliver_fit, deliver_pad_color=(0, 0, 0),
-            deliver_lut=None, deliver_interlace=a.deliver_interlace, deliver_lowpass=a.deliver_lowpass)
+            deliver_lut=None, deliver_interlace=a.deliver_interlace, deliver_lowpass=a.deliver_lowpass, in_chroma_rows=a.in_chroma_rows)
     try:
         refuse(v, "flags", early=True)
         if int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("CRTFX_FORCE_DIST") == "1":

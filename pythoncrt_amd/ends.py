@@ -50,14 +50,19 @@ class SourceEnd(StagingSlots):
     and on `dtype`, in front of the Deinterlace, the Canvas, the resize, the Widen and the Lut3D — the cable carried the fields and the
     source's own samples, one pixel being one sample at four times the colour subcarrier — for an rgb24 frame at render size the only
     stage.  Its frame index t is the source frame's index in the stream: the caller sets `index` to that of the batch's first frame
-    before convert() (0 until it does); several ends of one stream (a mixed-size rgb24 source) are each told."""
+    before convert() (0 until it does); several ends of one stream (a mixed-size rgb24 source) are each told.
+    `chroma_rows` says which luma rows a chroma row of a 4:2:0 source belongs to: "progressive" — rows 2c and 2c + 1, one of each field: in
+    front of a Deinterlace, a Signal or a probe the colour of the two fields is then already mixed — or "interlaced" — the rows of its own
+    field, as an interlaced encoder sub-samples them: the source plan is then an UnpackField420 (include/crtfx_field420.h) at `in_chroma`,
+    and the stages behind it read fields whose colour is their own."""
 
     def __init__(self, device, render_hw, in_pix_fmt, in_matrix, in_range, in_chroma, src_hw, in_filter, crop=None, dtype=None, widen=False,
-                 deinterlace=None, lut=None, signal=None):
+                 deinterlace=None, lut=None, signal=None, chroma_rows="progressive"):
         import torch
         self.device, self.src_hw = device, tuple(src_hw)
         self.dtype = torch.uint8 if dtype is None or widen else dtype      # widen: `dtype` is the chain's, the stages in front of it run on uint8
-        self.plan = formats.source_plan(device, self.src_hw, in_pix_fmt, in_matrix, in_range, in_chroma)
+        self.plan = formats.source_plan(device, self.src_hw, in_pix_fmt, in_matrix, in_range, in_chroma,
+                                        *(() if chroma_rows == "progressive" else (chroma_rows,)))
         self.signal, self.index = None, 0
         if signal is not None:
             self.signal = Signal(device, self.src_hw, signal=signal[0], chroma=signal[1], crawl=signal[2], dtype=self.dtype)

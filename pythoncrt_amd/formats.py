@@ -5,7 +5,7 @@ from __future__ import annotations
 
 from typing import Callable, NamedTuple, Tuple
 
-from . import deep, deep444, egress, sited, unpack, yuv422
+from . import deep, deep444, egress, field420, sited, unpack, yuv422
 
 
 class Family(NamedTuple):
@@ -35,10 +35,13 @@ def frame_bytes(h: int, w: int, fmt: str) -> int:
     return FORMATS[fmt].frame_bytes(int(h), int(w), fmt) if fmt in FORMATS else int(h) * int(w) * 3
 
 
-def source_plan(device, size, fmt: str, matrix: str, range: str, chroma: str):     # noqa: A002 - the stages' keyword
-    """The plan in front of the chain: None for "rgb24", the family's source under chroma "replicate", else UnpackSited at that siting."""
+def source_plan(device, size, fmt: str, matrix: str, range: str, chroma: str, rows: str = "progressive"):     # noqa: A002 - the stages' keyword
+    """The plan in front of the chain: None for "rgb24", the family's source under chroma "replicate", else UnpackSited at that siting.
+    With rows "interlaced" (a 4:2:0 format whose chroma rows alternate between the fields): UnpackField420 at that chroma."""
     if fmt == "rgb24":
         return None
+    if rows == "interlaced":
+        return field420.UnpackField420(device, size, layout=fmt, matrix=matrix, range=range, chroma=chroma)
     cls, siting = (FORMATS[fmt].source, {}) if chroma == "replicate" else (sited.UnpackSited, {"siting": chroma})
     return cls(device, size, layout=fmt, matrix=matrix, range=range, **siting)
 

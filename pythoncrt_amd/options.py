@@ -9,7 +9,7 @@ from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Callable, NamedTuple, Optional, Tuple
 
-from . import formats, render, sited, tables
+from . import field420, formats, render, sited, tables
 from .adeint import METHOD as ADAPTIVE
 from .cube import Cube, as_cube
 from .deint import FIELDS, METHODS as SPATIAL, ORDERS
@@ -35,6 +35,13 @@ class Raw(SimpleNamespace):
     crop_bounds = property(lambda v: None if v.in_pix_fmt == "rgb24" else v.src_hw)
     rows = property(lambda v: (v.deliver_size or v.render_hw)[0])      # of a delivered frame; None: the CLI's --height, not checked yet
     crawl = property(lambda v: "on" if v.signal_crawl else "off")
+    in_chroma_rows = "progressive"      # unless the surface says otherwise
+
+    @property
+    def src_rows(v):
+        """The rows of a source frame where the options fix them; None for rgb24 frames and for a --height not checked yet."""
+        size = v.in_size if v.in_size is not None else v.render_hw if v.in_pix_fmt != "rgb24" else None
+        return None if size is None or size[0] is None else int(size[0])
 
     @property
     def src_hw(v):
@@ -154,10 +161,27 @@ RULES = (
 )
 
 
+CHROMA_ROWS = ("progressive", "interlaced")
+FIELD420 = f"({', '.join(field420.LAYOUTS)})"
+
+# What in_chroma_rows adds, walked behind RULES: a table of its own, every entry in front of the sharded CLI's branch.
+FIELD_RULES = (
+    Rule("in_chroma_rows", lambda v: not isinstance(v.in_chroma_rows, str) or v.in_chroma_rows not in CHROMA_ROWS,
+         "in_chroma_rows must be 'progressive' or 'interlaced', got {v.in_chroma_rows!r}", early=True),
+    Rule("in_chroma_rows_format", lambda v: v.in_chroma_rows == "interlaced" and v.in_pix_fmt not in field420.LAYOUTS,
+         "in_chroma_rows='interlaced' with in_pix_fmt={v.in_pix_fmt!r}: only a 4:2:0 input has chroma rows that two fields share " + FIELD420,
+         "--in-chroma-rows interlaced with --in-pix-fmt {v.in_pix_fmt}: only a 4:2:0 input has chroma rows that two fields share " + FIELD420, early=True),
+    Rule("in_chroma_rows_height", lambda v: v.in_chroma_rows == "interlaced" and v.src_rows is not None and (v.src_rows % 2 == 1 or v.src_rows < field420.MIN_ROWS),
+         "in_chroma_rows='interlaced': a source frame of {v.src_rows} row(s) has no two fields of whole chroma rows (an even height of at least 4)",
+         "--in-chroma-rows interlaced with --height {v.src_rows}: a frame of {v.src_rows} row(s) has no two fields of whole chroma rows "
+         "(an even height of at least 4)", early=True),
+)
+
+
 def refuse(v: Raw, surface: str, early: Optional[bool] = None) -> None:
-    """Walk RULES over `v` for `surface` ("keywords" or "flags") and raise OptionError with the first message that applies.  `early`: only
-    the entries in front of (True) or behind (False) the CLI's sharded branch."""
-    for rule in RULES:
+    """Walk RULES, then FIELD_RULES, over `v` for `surface` ("keywords" or "flags") and raise OptionError with the first message that
+    applies.  `early`: only the entries in front of (True) or behind (False) the CLI's sharded branch."""
+    for rule in RULES + FIELD_RULES:
         text = getattr(rule, surface)
         if text is None or early not in (None, rule.early):
             continue
@@ -196,12 +220,15 @@ class ChainOptions:
     deliver_cube: Optional[Cube] = None
     weave: Optional[Tuple[str, str]] = None                     # (order, lowpass)
     resize_on: str = "device"
+    in_chroma_rows = "progressive"      # a constant here and a field of FieldChainOptions: see there
 
     @classmethod
     def build(cls, v: Raw, surface: Optional[str] = None) -> "ChainOptions":
         """The spec of raw values; with a surface they go through `refuse` first (OptionError), without one the caller has done that."""
         if surface is not None:
             refuse(v, surface)
+        if cls is ChainOptions and v.in_chroma_rows != "progressive":
+            return FieldChainOptions.build(v)
         return cls(render_hw=v.render_hw, in_pix_fmt=v.in_pix_fmt, in_matrix=v.in_matrix, in_range=v.in_range, in_chroma=v.in_chroma,
                    in_size=None if v.in_size is None else v.src_hw, in_filter=v.in_filter, crop=v.in_crop,
                    deinterlace=None if v.deinterlace == "off" else (v.deinterlace, v.field_order, v.deinterlace_fields),
@@ -240,7 +267,8 @@ class ChainOptions:
         from .ends import SourceEnd
         return SourceEnd(device, self.render_hw, self.in_pix_fmt, self.in_matrix, self.in_range, self.in_chroma, src_hw, self.in_filter, self.crop, pix,
                          widen=self.widen, deinterlace=self.deinterlace, **({} if self.in_cube is None else {"lut": self.in_cube}),
-                         **({} if self.signal is None else {"signal": self.signal}))
+                         **({} if self.signal is None else {"signal": self.signal}),
+                         **({} if self.in_chroma_rows == "progressive" else {"chroma_rows": self.in_chroma_rows}))
 
     def delivery_end(self, device, pix):
         """The DeliveryEnd behind a chain of `pix`."""
@@ -248,3 +276,11 @@ class ChainOptions:
         return DeliveryEnd(device, self.render_hw, pix, self.out_pix_fmt, self.out_matrix, self.out_range, self.out_chroma, self.deliver,
                            self.deliver_filter, self.deliver_fit, self.pad_color, narrow=self.narrow,
                            **({} if self.deliver_cube is None else {"lut": self.deliver_cube}), **({} if self.weave is None else {"interlace": self.weave}))
+
+
+@dataclass(frozen=True)
+class FieldChainOptions(ChainOptions):
+    """The spec of a source whose 4:2:0 chroma rows alternate between the fields: what `ChainOptions.build` returns for
+    in_chroma_rows="interlaced".  A class of its own because every defaulted field of ChainOptions is one that the recorded cases of
+    tests/test_chain_options.py move; "progressive" stays the base class's constant."""
+    in_chroma_rows: str = "interlaced"

@@ -226,7 +226,7 @@ class ProbeReport:
 
 # ---- a whole stream -------------------------------------------------------------------------------------------------------------------------
 
-def _refuse_input(out_w, out_h, in_pix_fmt, in_matrix, in_range, in_size, in_chroma, surface="keywords"):
+def _refuse_input(out_w, out_h, in_pix_fmt, in_matrix, in_range, in_size, in_chroma, surface="keywords", in_chroma_rows="progressive"):
     """The input keywords against options.RULES in `process_frames`' wording (or, for "flags", the CLI's): a Raw that holds its defaults for everything else — but for
     `out_pix_fmt`, which takes a 10-bit input's own name: the rule about one 10-bit end is about a delivery, and the probe has none."""
     from .options import Raw, refuse
@@ -235,23 +235,25 @@ def _refuse_input(out_w, out_h, in_pix_fmt, in_matrix, in_range, in_size, in_chr
             in_pix_fmt=in_pix_fmt, in_matrix=in_matrix, in_range=in_range, in_size=in_size, in_chroma=in_chroma, out_chroma="center",
             deliver_size=None, in_filter="bilinear", deliver_filter="bilinear", in_crop=None, deliver_fit="stretch", deliver_pad_color=(0, 0, 0),
             chain_pix="auto", dither="none", deinterlace="off", field_order="tff", deinterlace_fields="first", in_lut=None, deliver_lut=None,
-            deliver_interlace="off", deliver_lowpass="none", in_signal="rgb", signal_chroma="sharp", signal_crawl=True)
+            deliver_interlace="off", deliver_lowpass="none", in_signal="rgb", signal_chroma="sharp", signal_crawl=True, in_chroma_rows=in_chroma_rows)
     refuse(v, surface)
     return v.src_hw
 
 
 def probe_frames(frame_iter: Iterable[np.ndarray], out_w: int, out_h: int, *, in_pix_fmt: str = "rgb24", in_matrix: str = "bt601",
                  in_range: str = "tv", in_size: Optional[Tuple[int, int]] = None, in_chroma: str = "replicate",
-                 max_frames: Optional[int] = None, batch: int = 16, device=None) -> ProbeReport:
+                 max_frames: Optional[int] = None, batch: int = 16, device=None, in_chroma_rows: str = "progressive") -> ProbeReport:
     """Probe the frames of `frame_iter` — what `process_frames` would be given, with its input keywords — and return the ProbeReport.
     A packed `in_pix_fmt` has frames of `in_size` (default: out_h x out_w) as 1-D arrays of formats.frame_bytes bytes; they are staged in
     pinned memory, uploaded and converted to RGB by formats.source_plan as `process_frames` does, 10-bit formats to half frames.  "rgb24"
     frames are H x W x 3 arrays and are probed as they are, at their own size, which must be one size: a second size raises ValueError.
     `Probe.push` runs batch after batch of `batch` frames, so every frame but the first has a previous frame; the records are downloaded and
-    added to the report.  `max_frames` stops early.  The keywords are refused as `process_frames` refuses them (options.RULES, the same
+    added to the report.  `max_frames` stops early.  `in_chroma_rows="interlaced"` reads a 4:2:0 input as an interlaced encoder wrote it,
+    every luma row taking chroma from rows of its own field (UnpackField420, as under `process_frames`): the field-order measure then sees
+    the asymmetry of coloured motion undiminished.  The keywords are refused as `process_frames` refuses them (options.RULES, the same
     messages), before a device is touched."""
     import torch
-    src_hw = _refuse_input(out_w, out_h, in_pix_fmt, in_matrix, in_range, in_size, in_chroma)
+    src_hw = _refuse_input(out_w, out_h, in_pix_fmt, in_matrix, in_range, in_size, in_chroma, in_chroma_rows=in_chroma_rows)
     if max_frames is not None and int(max_frames) < 0:
         raise ValueError(f"max_frames must be None or >= 0, got {max_frames!r}")
     if not torch.cuda.is_available():
@@ -266,7 +268,8 @@ def probe_frames(frame_iter: Iterable[np.ndarray], out_w: int, out_h: int, *, in
         shape = (formats.frame_bytes(hw[0], hw[1], in_pix_fmt),) if packed else hw + (3,)
         state.update(hw=hw, shape=shape, report=ProbeReport(hw), pin=torch.empty((B,) + shape, dtype=torch.uint8).pin_memory(),
                      dev=torch.empty((B,) + shape, dtype=torch.uint8, device=dev),
-                     source=formats.source_plan(dev, hw, in_pix_fmt, in_matrix, in_range, in_chroma),
+                     source=formats.source_plan(dev, hw, in_pix_fmt, in_matrix, in_range, in_chroma,
+                                                *(() if in_chroma_rows == "progressive" else (in_chroma_rows,))),
                      probe=Probe(dev, hw, dtype=torch.float16 if deep else torch.uint8))
         state["np"] = state["pin"].numpy()
 
@@ -319,9 +322,9 @@ def build_parser():
     p.add_argument("--input", type=str, required=True, metavar="FILE|-", help="raw frames of --in-pix-fmt at --width x --height; - = standard input")
     p.add_argument("--width", type=int, required=True)
     p.add_argument("--height", type=int, required=True)
-    full = cli.add_input_flags(argparse.ArgumentParser(add_help=False))      # cli's own choices and help of the four flags, not restated
+    full = cli.add_input_flags(argparse.ArgumentParser(add_help=False))      # cli's own choices and help of the five flags, not restated
     for action in full._actions:
-        if action.option_strings and action.option_strings[0] in ("--in-pix-fmt", "--in-matrix", "--in-range", "--in-chroma"):
+        if action.option_strings and action.option_strings[0] in ("--in-pix-fmt", "--in-matrix", "--in-range", "--in-chroma", "--in-chroma-rows"):
             p.add_argument(*action.option_strings, type=action.type, default=action.default, choices=action.choices, help=action.help)
     p.add_argument("--frames", type=int, default=0, metavar="N", help="probe the first N frames only; 0 (default) = the whole input")
     p.add_argument("--json", action="store_true", help="print the whole report as one JSON object instead of the line of flags")
@@ -339,7 +342,7 @@ def main(argv=None) -> int:
     if a.frames < 0:
         raise SystemExit(f"--frames {a.frames}: pass a count, or 0 for the whole input")
     try:
-        _refuse_input(a.width, a.height, a.in_pix_fmt, a.in_matrix, a.in_range, None, a.in_chroma, "flags")
+        _refuse_input(a.width, a.height, a.in_pix_fmt, a.in_matrix, a.in_range, None, a.in_chroma, "flags", a.in_chroma_rows)
     except OptionError as e:
         raise SystemExit(str(e)) from e
     fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb")
@@ -348,7 +351,7 @@ def main(argv=None) -> int:
         if a.in_pix_fmt == "rgb24":
             items = (f.reshape(a.height, a.width, 3) for f in items)
         report = probe_frames(items, a.width, a.height, in_pix_fmt=a.in_pix_fmt, in_matrix=a.in_matrix, in_range=a.in_range,
-                              in_chroma=a.in_chroma, max_frames=a.frames or None)
+                              in_chroma=a.in_chroma, max_frames=a.frames or None, in_chroma_rows=a.in_chroma_rows)
     finally:
         if fin is not sys.stdin.buffer:
             fin.close()

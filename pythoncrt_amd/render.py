@@ -151,7 +151,8 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                    deliver_fit: str = "stretch", deliver_pad_color: Tuple[int, int, int] = (0, 0, 0), chain_pix: str = "auto",
                    dither: str = "none", deinterlace: str = "off", field_order: str = "tff", deinterlace_fields: str = "first",
                    in_lut=None, deliver_lut=None, deliver_interlace: str = "off", deliver_lowpass: str = "none",
-                   in_signal: str = "rgb", signal_chroma: str = "sharp", signal_crawl: bool = True, **io_keywords) -> int:
+                   in_signal: str = "rgb", signal_chroma: str = "sharp", signal_crawl: bool = True, in_chroma_rows: str = "progressive",
+                   **io_keywords) -> int:
     """Render every frame of `frame_iter` (H x W x 3 uint8 RGB arrays) and hand the finished uint8 frames to `write_frame` in order.
     Effect keywords: the names, meaning and defaults of process_video / the CLI (ref:864-911, :1155-1206); the caller applies the clamps of
     ref:1225-1266 as the reference's `main` does (`pythoncrt_amd.cli.settings_from_args` restates them).  Returns the number of frames written.
@@ -257,8 +258,9 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     the return value count frames WRITTEN (pass `total_frames` as such); the chain's clock stays `fps_out` as given: pass the FIELD rate
     (59.94 for 29.97i).  Every source then goes through a source end, as under `in_crop` or `chain_pix="half"` — an rgb24 frame at render
     size too — and an rgb24 frame of fewer than 2 rows raises ValueError.  "off" (default) is the path as it was: no Deinterlace is
-    created.  Known limit, under every method: the chroma rows of a 4:2:0 source are paired by its source plan as a progressive frame's
-    are, in front of this stage; 4:2:2, 4:4:4 and rgb24 sources have no such pairing.  Refused with ValueError before a device is touched: an unknown value of
+    created.  Under every method the chroma rows of a 4:2:0 source are paired by its source plan as a progressive frame's are, in front of
+    this stage, unless `in_chroma_rows="interlaced"` says that the fields were sub-sampled apart (below); 4:2:2, 4:4:4 and rgb24 sources
+    have no such pairing.  Refused with ValueError before a device is touched: an unknown value of
     the three keywords; `field_order` or `deinterlace_fields` off its default with "off" (there is nothing to deinterlace);
     `resize_on="host"`; a source height below 2 where it is known (`in_size`, or the render size for a packed `in_pix_fmt`).
     `in_lut` / `deliver_lut` put a 3D colour LUT directly in front of the chain and directly behind it: a path to a `.cube` file or a
@@ -305,6 +307,15 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     chroma rows of a 4:2:0 source are formed in front of the stage by its source plan.  Refused with ValueError before a device is
     touched: an unknown value of the three keywords; `signal_chroma` or `signal_crawl` off its default with "rgb" (there is no signal);
     `resize_on="host"`.
+    `in_chroma_rows="interlaced"` reads a 4:2:0 input ("yuv420p", "nv12", "yuv420p10le", "p010le") as an interlaced encoder wrote it
+    (DVD, broadcast MPEG-2 and H.264 at 480i / 576i / 1080i, 10-bit HEVC at 1080i): chroma rows 0, 2, 4, ... belong to the top field and
+    rows 1, 3, 5, ... to the bottom field, so every luma row takes its colour from rows of its own field — UnpackField420
+    (include/crtfx_field420.h) then stands where the family's source plan or UnpackSited stood, at `in_chroma` ("replicate": the nearest
+    chroma row of the field; "left" / "center": interpolated at MPEG-2's interlaced vertical siting and that horizontal siting).  Pass it
+    with `deinterlace`: a deinterlacer, the Signal and the probe then read fields whose colour is their own, where under "progressive"
+    (default: the path as it was) frame rows 4j + 1 and 4j + 2 carry the other field's colour and coloured motion combs in a way no
+    deinterlacer can remove.  Refused with ValueError before a device is touched: an unknown value; "interlaced" with any other
+    `in_pix_fmt`; a source height that is known (`in_size`, or the render size) and is odd or below 4.
     If `frame_iter` or `write_frame` raises, the GPU work already queued is drained (device synchronize) before the exception leaves this
     function, so that the staging buffers are not freed under a running copy."""
     import os
@@ -321,7 +332,8 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         deliver_size=deliver_size, in_filter=in_filter, deliver_filter=deliver_filter, in_crop=in_crop, deliver_fit=deliver_fit,
         deliver_pad_color=deliver_pad_color, chain_pix=chain_pix, dither=dither, deinterlace=deinterlace, field_order=field_order,
         deinterlace_fields=deinterlace_fields, in_lut=in_lut, deliver_lut=deliver_lut, deliver_interlace=deliver_interlace,
-        deliver_lowpass=deliver_lowpass, in_signal=in_signal, signal_chroma=signal_chroma, signal_crawl=signal_crawl), "keywords")
+        deliver_lowpass=deliver_lowpass, in_signal=in_signal, signal_chroma=signal_chroma, signal_crawl=signal_crawl,
+        in_chroma_rows=in_chroma_rows), "keywords")
     crop, ratio, deep = spec.crop, spec.ratio, formats.bits(in_pix_fmt) == 10
     if not torch.cuda.is_available():
         raise RuntimeError("no ROCm device visible; pythoncrt_amd has no CPU fallback")
