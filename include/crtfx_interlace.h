@@ -31,8 +31,9 @@
  * stage writes ceil(n / 2) frames; the destination stride is per OUTPUT frame.  For half frames every frame base and frame stride must
  * be even (CRTFX_E_INVALID otherwise); uint8 frames may start anywhere.
  *
- * Stated limit: this stage weaves RGB rows.  The chroma rows of a 4:2:0 delivery are formed behind it by the egress plan as a progressive
- * frame's are, so they mix the two fields; 4:2:2, 4:4:4 and rgb24 deliveries have no such pairing.
+ * This stage weaves RGB rows.  The chroma rows of a 4:2:0 delivery are formed behind it: by the box and the sited egress stages as a
+ * progressive frame's are, so they mix the two fields, or — out_chroma_rows="interlaced" — by the field-paired egress stage
+ * (crtfx_egress_field420.h) from rows of their own field only; 4:2:2, 4:4:4 and rgb24 deliveries have no such pairing.
  *
  * Paths; both give the same bytes, the path is chosen per run, and *_last_plan names the one that ran.  The order only selects a frame
  * pointer and is a launch argument: twelve builds.

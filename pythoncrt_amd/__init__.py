@@ -11,6 +11,7 @@
     from pythoncrt_amd import UnpackSited         # the source step of every 4:2:0 / 4:2:2 format with chroma interpolated at its siting ("left" / "center")
     from pythoncrt_amd import EgressSited         # ... and the egress step of the same formats with chroma filtered onto that siting instead of box-averaged
     from pythoncrt_amd import UnpackField420      # the source step of INTERLACED 4:2:0 material: every luma row takes chroma from rows of its own field
+    from pythoncrt_amd import EgressField420      # ... and the egress step of an INTERLACED 4:2:0 delivery: every chroma sample formed from rows of its own field
     from pythoncrt_amd import ResizeHalf          # IngestResize for half frames: behind the chain, where process_frames(deliver_size=) delivers another size
     from pythoncrt_amd import Resample            # either of the two with a filter: box / bilinear / hamming / bicubic / lanczos, uint8 or half frames
     from pythoncrt_amd import Canvas              # crop and pad: a window of uint8 or half frames placed on a canvas of another size, the rest a colour
@@ -34,7 +35,7 @@ from .adeint import AdaptiveDeinterlace
 from .deint import Deinterlace
 from .deep444 import EgressDeep444, UnpackDeep444
 from .egress import EgressYuv
-from .field420 import UnpackField420
+from .field420 import EgressField420, UnpackField420
 from .ingest import IngestResize
 from .interlace import Interlace
 from .cube import Cube
@@ -49,7 +50,7 @@ from .yuv422 import EgressYuv422, UnpackYuv422
 
 __all__ = ["DeviceState", "TriadMask", "VignetteMask", "apply_crt_effect", "apply_static_effects", "make_triad_mask", "make_vignette",
            "process_frames", "iter_rgb24", "iter_yuv420", "IngestResize", "EgressYuv", "UnpackYuv", "EgressYuv10", "UnpackYuv10",
-           "iter_yuv422", "EgressYuv422", "UnpackYuv422", "iter_deep444", "EgressDeep444", "UnpackDeep444", "UnpackSited", "EgressSited", "UnpackField420", "ResizeHalf", "Resample", "Canvas", "Widen", "Narrow", "Deinterlace", "AdaptiveDeinterlace", "Lut3D", "Cube", "Interlace", "Signal", "Probe", "ProbeReport", "probe_frames"]
+           "iter_yuv422", "EgressYuv422", "UnpackYuv422", "iter_deep444", "EgressDeep444", "UnpackDeep444", "UnpackSited", "EgressSited", "UnpackField420", "EgressField420", "ResizeHalf", "Resample", "Canvas", "Widen", "Narrow", "Deinterlace", "AdaptiveDeinterlace", "Lut3D", "Cube", "Interlace", "Signal", "Probe", "ProbeReport", "probe_frames"]
 
 
 def __getattr__(name):

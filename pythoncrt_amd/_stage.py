@@ -1,7 +1,7 @@
 """What every plan object over a libcrtfx handle shares.  `Handle` is the handle of one crtfx_<family>_* family behind a plan object: device,
 create and its error path, options, the batched run, the plan string, close.  On it stand `StagePlan` — the ten format-stage plans
-(unpack.py, egress.py, deep.py, yuv422.py, deep444.py), the two sited plans (sited.py: source and egress) and the field-paired 4:2:0 source
-plan (field420.py), seven entry points each
+(unpack.py, egress.py, deep.py, yuv422.py, deep444.py), the two sited plans (sited.py: source and egress) and the two field-paired 4:2:0
+plans (field420.py: source and egress), seven entry points each
 (`_lib.stage_symbols`) — `ResizePlan` — the three resize plans (ingest.py, resize16.py, resample.py), six entry points each
 (`_lib.resize_symbols`) — and `FramePlan` — the nine plans of the eight frame stages (canvas.py, depth.py, deint.py, adeint.py, lut3d.py, interlace.py, signal.py, probe.py), six
 entry points and a create of its own each (`_lib.frame_symbols`).  A family module declares short classes on `SourcePlan` / `EgressPlan` /

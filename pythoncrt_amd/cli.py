@@ -106,6 +106,11 @@ one is woven with itself).  480i in, 480i out, for a DVD encoder:
              --deinterlace edge --field-order bff --deinterlace-fields both --deliver-interlace bff --deliver-lowpass linear [effect flags] |
       ffmpeg -f rawvideo -pix_fmt uyvy422 -s 720x480 -r 30000/1001 -i - -flags +ilme+ildct -field_order bb out.mpg
 
+With a 4:2:0 `--out-pix-fmt` (yuv420p, nv12, yuv420p10le, p010le), `--out-chroma-rows interlaced` forms chroma rows 0, 2, 4, ... from the top
+field's luma rows and rows 1, 3, 5, ... from the bottom field's (include/crtfx_egress_field420.h), as an interlaced decoder reads them;
+without it every chroma sample of a woven frame mixes the two fields and colour combs on motion.  `--out-chroma left` then means MPEG-2's
+interlaced siting.  The delivered height must be a multiple of 4 (480, 576 and 1080 are).
+
 `--in-signal composite|svideo` sends every input frame through the cable that fed the tube (include/crtfx_signal.h): every row is encoded
 to an NTSC-like signal and decoded again on the GPU, before anything else sees it — colour that bleeds sideways and, under `composite`, dot
 crawl on colour edges and rainbow fringes on fine luma detail; `svideo` keeps luma and chroma apart.  One pixel is one sample at four
@@ -274,6 +279,11 @@ def add_output_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--deliver-lowpass", type=str, default="none", choices=["none", "linear", "complex"],
                    help="vertical low-pass of every row inside its own frame before the weave, against line twitter: [1 2 1] / 4 (linear) or "
                         "[-1 2 6 2 -1] / 8 held back from over-sharpening (complex); none (default) copies rows; needs --deliver-interlace")
+    p.add_argument("--out-chroma-rows", type=str, default="progressive", choices=["progressive", "interlaced"],
+                   help="which luma rows a chroma row of a 4:2:0 --out-pix-fmt is formed from: rows 2c and 2c + 1, one of each field (progressive, "
+                        "default), or rows of the chroma row's own field only, as an interlaced decoder reads them (interlaced: "
+                        "include/crtfx_egress_field420.h; --out-chroma left is then MPEG-2's interlaced siting; the delivered height must be a "
+                        "multiple of 4)")
     return p
 
 
@@ -592,7 +602,8 @@ def check_flags(a):
             in_signal=a.in_signal, signal_chroma=a.signal_chroma, signal_crawl=a.signal_crawl == "on", in_lut=None, chain_pix=a.chain_pix,
             dither=a.dither, out_pix_fmt=a.out_pix_fmt, out_matrix=a.out_matrix, out_range=a.out_range, out_chroma=a.out_chroma,
             deliver_size=deliver_size_from_args(a), deliver_filter=a.deliver_filter, deliver_fit=a.deliver_fit, deliver_pad_color=(0, 0, 0),
-            deliver_lut=None, deliver_interlace=a.deliver_interlace, deliver_lowpass=a.deliver_lowpass, in_chroma_rows=a.in_chroma_rows)
+            deliver_lut=None, deliver_interlace=a.deliver_interlace, deliver_lowpass=a.deliver_lowpass, in_chroma_rows=a.in_chroma_rows,
+            out_chroma_rows=a.out_chroma_rows)
     try:
         refuse(v, "flags", early=True)
         if int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("CRTFX_FORCE_DIST") == "1":

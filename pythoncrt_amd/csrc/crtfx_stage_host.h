@@ -1,5 +1,5 @@
 // crtfx_stage_host.h — the host skeleton of the format stages (crtfx_unpack.hip, crtfx_egress.hip, crtfx_deep.hip, crtfx_422.hip,
-// crtfx_444.hip, crtfx_sited.hip, crtfx_egress_sited.hip, crtfx_field420.hip): what surrounds their kernels and does not depend on the format.  Host code only, and everything here is a template or
+// crtfx_444.hip, crtfx_sited.hip, crtfx_egress_sited.hip, crtfx_field420.hip, crtfx_egress_field420.hip): what surrounds their kernels and does not depend on the format.  Host code only, and everything here is a template or
 // sits in an unnamed namespace, so every translation unit that includes it gets a copy of its own: the units still share no state.  The resize
 // stages' skeleton (crtfx_resize_host.h: crtfx_ingest.hip, crtfx_resize16.hip, crtfx_resample.hip) takes DeviceGuard, create_err and fail from
 // here and nothing else; the frame stages' skeleton (crtfx_frame_host.h: crtfx_canvas.hip, crtfx_depth.hip, crtfx_deint.hip, crtfx_adeint.hip,

@@ -129,12 +129,14 @@ class DeliveryEnd:
     DELIVERY size and on `pix` then stands behind the delivery resize and the Canvas — a vertical resize would mix the fields — and in front
     of the Narrow and the egress plan: the low-pass runs at the chain's precision, the dither's coordinates are those of the delivered
     frame and the dither stays last.  It weaves two finished frames into one, an odd last frame of a run with itself: from it on every
-    buffer holds `frames(B)` = ceil(B / 2) frames, and run(d, m) returns frames(m).  Known limit: the chroma rows of a 4:2:0 delivery are
-    formed by the egress plan as a progressive frame's are, so they mix the two fields; 4:2:2, 4:4:4 and rgb24 deliveries have no such
-    pairing.  Everything downstream is in frames of `frame_bytes`, batches of `shape(frames(B))`."""
+    buffer holds `frames(B)` = ceil(B / 2) frames, and run(d, m) returns frames(m).  `chroma_rows` says which luma rows a chroma row of a
+    4:2:0 delivery is formed from: "progressive" — rows 2c and 2c + 1, one of each field, as the family's egress plan and EgressSited form
+    it — or "interlaced" — rows of the chroma row's own field only (EgressField420, include/crtfx_egress_field420.h; the delivered height
+    is a multiple of 4), as an interlaced decoder reads a woven frame; 4:2:2, 4:4:4 and rgb24 deliveries have no such pairing.  Everything
+    downstream is in frames of `frame_bytes`, batches of `shape(frames(B))`."""
 
     def __init__(self, device, render_hw, pix, out_pix_fmt, out_matrix, out_range, out_chroma, deliver, deliver_filter,
-                 deliver_fit="stretch", pad_color=(0, 0, 0), narrow=None, lut=None, interlace=None):
+                 deliver_fit="stretch", pad_color=(0, 0, 0), narrow=None, lut=None, interlace=None, chroma_rows="progressive"):
         self.device, self.pix = device, pix
         self.size = tuple(deliver) if deliver is not None else tuple(render_hw)
         self.resize = self.canvas = self.narrow = self.lut = self.interlace = None
@@ -165,7 +167,8 @@ class DeliveryEnd:
         if narrow is not None:
             self.narrow = Narrow(device, self.size, dither=narrow)
             self.stages.append((self.narrow, self.size))
-        self.egress = formats.egress_plan(device, self.size, out_pix_fmt, out_matrix, out_range, out_chroma)
+        self.egress = formats.egress_plan(device, self.size, out_pix_fmt, out_matrix, out_range, out_chroma,
+                                          *(() if chroma_rows == "progressive" else (chroma_rows,)))
         self.frame_bytes = self.size[0] * self.size[1] * 3 if self.egress is None else self.egress.frame_bytes
 
     def frames(self, m: int) -> int:

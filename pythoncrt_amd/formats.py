@@ -46,9 +46,12 @@ def source_plan(device, size, fmt: str, matrix: str, range: str, chroma: str, ro
     return cls(device, size, layout=fmt, matrix=matrix, range=range, **siting)
 
 
-def egress_plan(device, size, fmt: str, matrix: str, range: str, chroma: str):     # noqa: A002
-    """The plan behind the chain: None for "rgb24", the family's egress under chroma "center" (the box mean), else EgressSited at "left"."""
+def egress_plan(device, size, fmt: str, matrix: str, range: str, chroma: str, rows: str = "progressive"):     # noqa: A002
+    """The plan behind the chain: None for "rgb24", the family's egress under chroma "center" (the box mean), else EgressSited at "left".
+    With rows "interlaced" (a 4:2:0 format whose chroma rows alternate between the fields): EgressField420 at that chroma."""
     if fmt == "rgb24":
         return None
+    if rows == "interlaced":
+        return field420.EgressField420(device, size, layout=fmt, matrix=matrix, range=range, chroma=chroma)
     cls, siting = (FORMATS[fmt].egress, {}) if chroma == "center" else (sited.EgressSited, {"siting": chroma})
     return cls(device, size, layout=fmt, matrix=matrix, range=range, **siting)

@@ -22,8 +22,9 @@ class Interlace(FramePlan):
     torch.float16.  `frames` and `out` are tensors on `device` whose frames are contiguous (the batch stride is free: slices of larger
     tensors are fine).  The work is enqueued on the current stream of `device`; nothing synchronises.  plan.plan() is
     crtfx_interlace_last_plan as a dictionary, e.g. {"interlace": "k_interlace<linear,u8,vec>", "frames": "6"} (the SOURCE frames of the
-    run).  Stated limit: the chroma rows of a 4:2:0 delivery are formed behind this stage by the egress plan as a progressive frame's are,
-    so they mix the two fields; 4:2:2, 4:4:4 and rgb24 deliveries have no such pairing."""
+    run).  The chroma rows of a 4:2:0 delivery are formed behind this stage: by the family's egress plan and EgressSited as a progressive
+    frame's are, so they mix the two fields, or by EgressField420 (out_chroma_rows="interlaced") from rows of their own field only; 4:2:2,
+    4:4:4 and rgb24 deliveries have no such pairing."""
     _family = "interlace"
     _force_option = _lib.INTERLACE_OPT_FORCE_GENERAL
     frames_in = 2

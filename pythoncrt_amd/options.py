@@ -36,6 +36,7 @@ class Raw(SimpleNamespace):
     rows = property(lambda v: (v.deliver_size or v.render_hw)[0])      # of a delivered frame; None: the CLI's --height, not checked yet
     crawl = property(lambda v: "on" if v.signal_crawl else "off")
     in_chroma_rows = "progressive"      # unless the surface says otherwise
+    out_chroma_rows = "progressive"     # likewise
 
     @property
     def src_rows(v):
@@ -178,10 +179,26 @@ FIELD_RULES = (
 )
 
 
+# What out_chroma_rows adds, walked behind FIELD_RULES: again a table of its own, every entry in front of the sharded CLI's branch.  It does
+# not ask for deliver_interlace: a woven source passed through undeinterlaced is interlaced too.
+OUT_FIELD_RULES = (
+    Rule("out_chroma_rows", lambda v: not isinstance(v.out_chroma_rows, str) or v.out_chroma_rows not in CHROMA_ROWS,
+         "out_chroma_rows must be 'progressive' or 'interlaced', got {v.out_chroma_rows!r}", early=True),
+    Rule("out_chroma_rows_format", lambda v: v.out_chroma_rows == "interlaced" and v.out_pix_fmt not in field420.LAYOUTS,
+         "out_chroma_rows='interlaced' with out_pix_fmt={v.out_pix_fmt!r}: only a 4:2:0 output has chroma rows that two fields share " + FIELD420,
+         "--out-chroma-rows interlaced with --out-pix-fmt {v.out_pix_fmt}: only a 4:2:0 output has chroma rows that two fields share " + FIELD420, early=True),
+    Rule("out_chroma_rows_height", lambda v: v.out_chroma_rows == "interlaced" and v.rows is not None and (v.rows % field420.EGRESS_ROWS != 0 or v.rows < field420.EGRESS_ROWS),
+         "out_chroma_rows='interlaced': a delivered frame of {v.rows} row(s) has no two fields with whole pairs of luma rows under their chroma rows "
+         "(a height that is a multiple of 4)",
+         "--out-chroma-rows interlaced with a delivery height of {v.rows}: a frame of {v.rows} row(s) has no two fields with whole pairs of luma rows "
+         "under their chroma rows (a height that is a multiple of 4)", early=True),
+)
+
+
 def refuse(v: Raw, surface: str, early: Optional[bool] = None) -> None:
-    """Walk RULES, then FIELD_RULES, over `v` for `surface` ("keywords" or "flags") and raise OptionError with the first message that
+    """Walk RULES, then FIELD_RULES, then OUT_FIELD_RULES, over `v` for `surface` ("keywords" or "flags") and raise OptionError with the first message that
     applies.  `early`: only the entries in front of (True) or behind (False) the CLI's sharded branch."""
-    for rule in RULES + FIELD_RULES:
+    for rule in RULES + FIELD_RULES + OUT_FIELD_RULES:
         text = getattr(rule, surface)
         if text is None or early not in (None, rule.early):
             continue
@@ -221,15 +238,17 @@ class ChainOptions:
     weave: Optional[Tuple[str, str]] = None                     # (order, lowpass)
     resize_on: str = "device"
     in_chroma_rows = "progressive"      # a constant here and a field of FieldChainOptions: see there
+    out_chroma_rows = "progressive"     # likewise
 
     @classmethod
     def build(cls, v: Raw, surface: Optional[str] = None) -> "ChainOptions":
         """The spec of raw values; with a surface they go through `refuse` first (OptionError), without one the caller has done that."""
         if surface is not None:
             refuse(v, surface)
-        if cls is ChainOptions and v.in_chroma_rows != "progressive":
+        if cls is ChainOptions and (v.in_chroma_rows != "progressive" or v.out_chroma_rows != "progressive"):
             return FieldChainOptions.build(v)
-        return cls(render_hw=v.render_hw, in_pix_fmt=v.in_pix_fmt, in_matrix=v.in_matrix, in_range=v.in_range, in_chroma=v.in_chroma,
+        rows = {} if cls is ChainOptions else {"in_chroma_rows": v.in_chroma_rows, "out_chroma_rows": v.out_chroma_rows}
+        return cls(**rows, render_hw=v.render_hw, in_pix_fmt=v.in_pix_fmt, in_matrix=v.in_matrix, in_range=v.in_range, in_chroma=v.in_chroma,
                    in_size=None if v.in_size is None else v.src_hw, in_filter=v.in_filter, crop=v.in_crop,
                    deinterlace=None if v.deinterlace == "off" else (v.deinterlace, v.field_order, v.deinterlace_fields),
                    signal=None if v.in_signal == "rgb" else (v.in_signal, v.signal_chroma, v.signal_crawl), in_cube=v.in_lut,
@@ -275,12 +294,14 @@ class ChainOptions:
         from .ends import DeliveryEnd
         return DeliveryEnd(device, self.render_hw, pix, self.out_pix_fmt, self.out_matrix, self.out_range, self.out_chroma, self.deliver,
                            self.deliver_filter, self.deliver_fit, self.pad_color, narrow=self.narrow,
-                           **({} if self.deliver_cube is None else {"lut": self.deliver_cube}), **({} if self.weave is None else {"interlace": self.weave}))
+                           **({} if self.deliver_cube is None else {"lut": self.deliver_cube}), **({} if self.weave is None else {"interlace": self.weave}),
+                           **({} if self.out_chroma_rows == "progressive" else {"chroma_rows": self.out_chroma_rows}))
 
 
 @dataclass(frozen=True)
 class FieldChainOptions(ChainOptions):
-    """The spec of a source whose 4:2:0 chroma rows alternate between the fields: what `ChainOptions.build` returns for
-    in_chroma_rows="interlaced".  A class of its own because every defaulted field of ChainOptions is one that the recorded cases of
-    tests/test_chain_options.py move; "progressive" stays the base class's constant."""
+    """The spec of a source or a delivery whose 4:2:0 chroma rows alternate between the fields: what `ChainOptions.build` returns for
+    in_chroma_rows="interlaced", out_chroma_rows="interlaced" or both.  A class of its own because every defaulted field of ChainOptions
+    is one that the recorded cases of tests/test_chain_options.py move; "progressive" stays the base class's constant for both."""
     in_chroma_rows: str = "interlaced"
+    out_chroma_rows: str = "progressive"

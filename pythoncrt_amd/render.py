@@ -152,7 +152,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                    dither: str = "none", deinterlace: str = "off", field_order: str = "tff", deinterlace_fields: str = "first",
                    in_lut=None, deliver_lut=None, deliver_interlace: str = "off", deliver_lowpass: str = "none",
                    in_signal: str = "rgb", signal_chroma: str = "sharp", signal_crawl: bool = True, in_chroma_rows: str = "progressive",
-                   **io_keywords) -> int:
+                   out_chroma_rows: str = "progressive", **io_keywords) -> int:
     """Render every frame of `frame_iter` (H x W x 3 uint8 RGB arrays) and hand the finished uint8 frames to `write_frame` in order.
     Effect keywords: the names, meaning and defaults of process_video / the CLI (ref:864-911, :1155-1206); the caller applies the clamps of
     ref:1225-1266 as the reference's `main` does (`pythoncrt_amd.cli.settings_from_args` restates them).  Returns the number of frames written.
@@ -288,9 +288,9 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     straddles a batch: a batch with an odd frame count has its last frame woven with itself.  That happens at the end of the stream, and
     at a change of source size in a mixed rgb24 stream when no deinterlacer doubles the frames.  `written`, `progress_cb`, the return
     value and `total_frames` count DELIVERED frames; the chain's frame indices and its clock are unchanged: pass the field rate as
-    `fps_out`.  "off" (default) builds no plan and no buffer: the path as it was.  Known limit: the chroma rows of a 4:2:0 delivery are
-    formed by the egress plan as a progressive frame's are, so they mix the two fields; 4:2:2, 4:4:4 and rgb24 deliveries have no such
-    pairing.  Refused with ValueError before a device is touched: an unknown value of either keyword; `deliver_lowpass` other than "none"
+    `fps_out`.  "off" (default) builds no plan and no buffer: the path as it was.  The chroma rows of a 4:2:0 delivery are formed
+    by the egress plan as a progressive frame's are, so they mix the two fields, unless `out_chroma_rows="interlaced"` is passed (below);
+    4:2:2, 4:4:4 and rgb24 deliveries have no such pairing.  Refused with ValueError before a device is touched: an unknown value of either keyword; `deliver_lowpass` other than "none"
     with "off" (there is nothing to filter); a delivery height below 2.
     `in_signal="composite"` / `"svideo"` sends every source frame through the cable that fed the tube: a Signal (include/crtfx_signal.h)
     encodes every row to an NTSC-like signal and decodes it again on the device — colour that bleeds sideways and, under "composite", dot
@@ -316,6 +316,15 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     (default: the path as it was) frame rows 4j + 1 and 4j + 2 carry the other field's colour and coloured motion combs in a way no
     deinterlacer can remove.  Refused with ValueError before a device is touched: an unknown value; "interlaced" with any other
     `in_pix_fmt`; a source height that is known (`in_size`, or the render size) and is odd or below 4.
+    `out_chroma_rows="interlaced"` writes a 4:2:0 output ("yuv420p", "nv12", "yuv420p10le", "p010le") as an interlaced decoder reads it:
+    chroma rows 0, 2, 4, ... are formed from the top field's luma rows and rows 1, 3, 5, ... from the bottom field's — EgressField420
+    (include/crtfx_egress_field420.h) then stands where the family's egress plan or EgressSited stood, at `out_chroma` ("center": the box
+    mean inside the field; "left": MPEG-2's interlaced vertical siting and that horizontal siting).  Pass it with `deliver_interlace`, or
+    with a woven source that runs through undeinterlaced: under "progressive" (default: the path as it was) every chroma sample of such a
+    frame is the mean of one row of each field, two moments apart, and colour combs on motion in every interlaced decoder.  With
+    `in_chroma_rows="interlaced"`, `deinterlace_fields="both"` and `deliver_interlace` an interlaced 4:2:0 round trip stays on the device.
+    Refused with ValueError before a device is touched: an unknown value; "interlaced" with any other `out_pix_fmt`; a delivered height
+    (`deliver_size`, or the render size) that is no multiple of 4.
     If `frame_iter` or `write_frame` raises, the GPU work already queued is drained (device synchronize) before the exception leaves this
     function, so that the staging buffers are not freed under a running copy."""
     import os
@@ -333,7 +342,7 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         deliver_pad_color=deliver_pad_color, chain_pix=chain_pix, dither=dither, deinterlace=deinterlace, field_order=field_order,
         deinterlace_fields=deinterlace_fields, in_lut=in_lut, deliver_lut=deliver_lut, deliver_interlace=deliver_interlace,
         deliver_lowpass=deliver_lowpass, in_signal=in_signal, signal_chroma=signal_chroma, signal_crawl=signal_crawl,
-        in_chroma_rows=in_chroma_rows), "keywords")
+        in_chroma_rows=in_chroma_rows, out_chroma_rows=out_chroma_rows), "keywords")
     crop, ratio, deep = spec.crop, spec.ratio, formats.bits(in_pix_fmt) == 10
     if not torch.cuda.is_available():
         raise RuntimeError("no ROCm device visible; pythoncrt_amd has no CPU fallback")
