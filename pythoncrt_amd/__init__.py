@@ -20,6 +20,7 @@
     from pythoncrt_amd import AdaptiveDeinterlace # ... motion-adaptive: the other field woven in where the picture stood still, "edge" where it moved
     from pythoncrt_amd import Interlace           # interlace / tinterlace's place: two finished frames woven into one 1080i / 576i / 480i frame, with a low-pass
     from pythoncrt_amd import Signal              # the cable: an NTSC-like composite / S-Video encode and decode of every row: bleed, dot crawl, rainbows
+    from pythoncrt_amd import PalSignal           # ... and the PAL one: 270 degrees per line, the V switch, a delay-line decoder with a phase error
     from pythoncrt_amd import probe_frames        # cropdetect / idet / signalstats' place: letterbox, field order and levels measured on the device,
     from pythoncrt_amd import Probe, ProbeReport  # ... as keywords for process_frames; the plan that writes the records, the report that reads them
     from pythoncrt_amd import Lut3D, Cube         # lut3d=: a .cube colour LUT applied with tetrahedral interpolation, uint8 or half frames
@@ -40,6 +41,7 @@ from .ingest import IngestResize
 from .interlace import Interlace
 from .cube import Cube
 from .lut3d import Lut3D
+from .pal import PalSignal
 from .resize16 import ResizeHalf
 from .resample import Resample
 from .render import iter_deep444, iter_rgb24, iter_yuv420, iter_yuv422, process_frames
@@ -50,7 +52,7 @@ from .yuv422 import EgressYuv422, UnpackYuv422
 
 __all__ = ["DeviceState", "TriadMask", "VignetteMask", "apply_crt_effect", "apply_static_effects", "make_triad_mask", "make_vignette",
            "process_frames", "iter_rgb24", "iter_yuv420", "IngestResize", "EgressYuv", "UnpackYuv", "EgressYuv10", "UnpackYuv10",
-           "iter_yuv422", "EgressYuv422", "UnpackYuv422", "iter_deep444", "EgressDeep444", "UnpackDeep444", "UnpackSited", "EgressSited", "UnpackField420", "EgressField420", "ResizeHalf", "Resample", "Canvas", "Widen", "Narrow", "Deinterlace", "AdaptiveDeinterlace", "Lut3D", "Cube", "Interlace", "Signal", "Probe", "ProbeReport", "probe_frames"]
+           "iter_yuv422", "EgressYuv422", "UnpackYuv422", "iter_deep444", "EgressDeep444", "UnpackDeep444", "UnpackSited", "EgressSited", "UnpackField420", "EgressField420", "ResizeHalf", "Resample", "Canvas", "Widen", "Narrow", "Deinterlace", "AdaptiveDeinterlace", "Lut3D", "Cube", "Interlace", "Signal", "PalSignal", "Probe", "ProbeReport", "probe_frames"]
 
 
 def __getattr__(name):

@@ -14,9 +14,9 @@ LIB_PATH = os.environ.get("CRTFX_LIB") or os.path.join(_HERE, "libcrtfx.so")   #
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = [os.path.join(CSRC, f) for f in ("crtfx.hip", "crtfx_rr.hip", "crtfx_kernels.hip.h", "crtfx_common.hip.h", "crtfx_blur.hip.h", "crtfx_point.hip.h",
                                                 "crtfx_phosphor.hip.h", "crtfx_phosphor_ct.hip.h", "crtfx_warp.hip.h", "crtfx_internal.h", "crtfx_ingest.hip",
-                                                "crtfx_egress.hip", "crtfx_unpack.hip", "crtfx_deep.hip", "crtfx_422.hip", "crtfx_444.hip", "crtfx_sited.hip", "crtfx_egress_sited.hip", "crtfx_field420.hip", "crtfx_egress_field420.hip", "crtfx_resize16.hip", "crtfx_resample.hip", "crtfx_canvas.hip", "crtfx_depth.hip", "crtfx_deint.hip", "crtfx_adeint.hip", "crtfx_edge.hip.h", "crtfx_lut3d.hip", "crtfx_interlace.hip", "crtfx_signal.hip", "crtfx_probe.hip", "crtfx_stage_host.h", "crtfx_resize_host.h", "crtfx_frame_host.h")] + \
-          [os.path.join(ROOT, "include", f) for f in ("crtfx.h", "crtfx_ingest.h", "crtfx_egress.h", "crtfx_unpack.h", "crtfx_deep.h", "crtfx_422.h", "crtfx_444.h", "crtfx_sited.h", "crtfx_egress_sited.h", "crtfx_field420.h", "crtfx_egress_field420.h", "crtfx_resize16.h", "crtfx_resample.h", "crtfx_canvas.h", "crtfx_depth.h", "crtfx_deint.h", "crtfx_adeint.h", "crtfx_lut3d.h", "crtfx_interlace.h", "crtfx_signal.h", "crtfx_probe.h")]
-STAGE_UNITS = ("crtfx_ingest", "crtfx_egress", "crtfx_unpack", "crtfx_deep", "crtfx_422", "crtfx_444", "crtfx_sited", "crtfx_egress_sited", "crtfx_field420", "crtfx_egress_field420", "crtfx_resize16", "crtfx_resample", "crtfx_canvas", "crtfx_depth", "crtfx_deint", "crtfx_adeint", "crtfx_lut3d", "crtfx_interlace", "crtfx_signal", "crtfx_probe")   # one object file each, beside crtfx.hip / crtfx_rr.hip
+                                                "crtfx_egress.hip", "crtfx_unpack.hip", "crtfx_deep.hip", "crtfx_422.hip", "crtfx_444.hip", "crtfx_sited.hip", "crtfx_egress_sited.hip", "crtfx_field420.hip", "crtfx_egress_field420.hip", "crtfx_resize16.hip", "crtfx_resample.hip", "crtfx_canvas.hip", "crtfx_depth.hip", "crtfx_deint.hip", "crtfx_adeint.hip", "crtfx_edge.hip.h", "crtfx_lut3d.hip", "crtfx_interlace.hip", "crtfx_signal.hip", "crtfx_pal.hip", "crtfx_probe.hip", "crtfx_stage_host.h", "crtfx_resize_host.h", "crtfx_frame_host.h")] + \
+          [os.path.join(ROOT, "include", f) for f in ("crtfx.h", "crtfx_ingest.h", "crtfx_egress.h", "crtfx_unpack.h", "crtfx_deep.h", "crtfx_422.h", "crtfx_444.h", "crtfx_sited.h", "crtfx_egress_sited.h", "crtfx_field420.h", "crtfx_egress_field420.h", "crtfx_resize16.h", "crtfx_resample.h", "crtfx_canvas.h", "crtfx_depth.h", "crtfx_deint.h", "crtfx_adeint.h", "crtfx_lut3d.h", "crtfx_interlace.h", "crtfx_signal.h", "crtfx_pal.h", "crtfx_probe.h")]
+STAGE_UNITS = ("crtfx_ingest", "crtfx_egress", "crtfx_unpack", "crtfx_deep", "crtfx_422", "crtfx_444", "crtfx_sited", "crtfx_egress_sited", "crtfx_field420", "crtfx_egress_field420", "crtfx_resize16", "crtfx_resample", "crtfx_canvas", "crtfx_depth", "crtfx_deint", "crtfx_adeint", "crtfx_lut3d", "crtfx_interlace", "crtfx_signal", "crtfx_pal", "crtfx_probe")   # one object file each, beside crtfx.hip / crtfx_rr.hip
 RR_RADII = tuple(range(1, 31))      # one register-window build per radius up to 30 (crtfx_internal.h); larger radii: the split path
 
 OK, E_INVALID, E_HIP, E_UNSUPPORTED, E_NOMEM = 0, -1, -2, -3, -4
@@ -247,6 +247,15 @@ SIGNAL_OPT_FORCE_GENERAL = 1
 SIGNAL_SYMBOLS = frame_symbols("signal", [ctypes.c_int] * 6,
                                run=(ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]))
 
+# ... and every symbol include/crtfx_pal.h declares (the PAL composite-video stage, uint8 and half: a handle of its own, pythoncrt_amd/pal.py;
+# its create — device, h, w, pix_fmt, signal, chroma, crawl, decoder, phase, &plan — a run that takes the first frame's index in the stream
+# first, as the signal stage's, and phase_table, which needs no plan; the signal and chroma numbers are SIGNAL_*)
+PAL_DELAY, PAL_SIMPLE = 0, 1
+PAL_OPT_FORCE_GENERAL = 1
+PAL_SYMBOLS = frame_symbols("pal", [ctypes.c_int] * 8,
+                            run=(ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
+                            phase_table=(ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]))
+
 # ... and every symbol include/crtfx_probe.h declares (the source probe, uint8 and half: a handle of its own, pythoncrt_amd/probe.py; its
 # create — device, h, w, pix_fmt, &plan — a run that takes the previous frame first, as adeint's, and writes records, and words, which needs no plan)
 PROBE_OPT_FORCE_GENERAL = 1
@@ -334,7 +343,7 @@ def load() -> ctypes.CDLL:
             "pythoncrt_amd has no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in {**SYMBOLS, **INGEST_SYMBOLS, **EGRESS_SYMBOLS, **UNPACK_SYMBOLS, **DEEP_SYMBOLS, **YUV422_SYMBOLS, **DEEP444_SYMBOLS,
-                               **SITED_SYMBOLS, **EGRESS_SITED_SYMBOLS, **FIELD420_SYMBOLS, **EGRESS_FIELD420_SYMBOLS, **RESIZE16_SYMBOLS, **RESAMPLE_SYMBOLS, **CANVAS_SYMBOLS, **DEPTH_SYMBOLS, **DEINT_SYMBOLS, **ADEINT_SYMBOLS, **LUT3D_SYMBOLS, **INTERLACE_SYMBOLS, **SIGNAL_SYMBOLS, **PROBE_SYMBOLS}.items():
+                               **SITED_SYMBOLS, **EGRESS_SITED_SYMBOLS, **FIELD420_SYMBOLS, **EGRESS_FIELD420_SYMBOLS, **RESIZE16_SYMBOLS, **RESAMPLE_SYMBOLS, **CANVAS_SYMBOLS, **DEPTH_SYMBOLS, **DEINT_SYMBOLS, **ADEINT_SYMBOLS, **LUT3D_SYMBOLS, **INTERLACE_SYMBOLS, **SIGNAL_SYMBOLS, **PAL_SYMBOLS, **PROBE_SYMBOLS}.items():
         fn = getattr(lib, name)   # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

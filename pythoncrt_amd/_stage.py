@@ -3,7 +3,7 @@ create and its error path, options, the batched run, the plan string, close.  On
 (unpack.py, egress.py, deep.py, yuv422.py, deep444.py), the two sited plans (sited.py: source and egress) and the two field-paired 4:2:0
 plans (field420.py: source and egress), seven entry points each
 (`_lib.stage_symbols`) — `ResizePlan` — the three resize plans (ingest.py, resize16.py, resample.py), six entry points each
-(`_lib.resize_symbols`) — and `FramePlan` — the nine plans of the eight frame stages (canvas.py, depth.py, deint.py, adeint.py, lut3d.py, interlace.py, signal.py, probe.py), six
+(`_lib.resize_symbols`) — and `FramePlan` — the ten plans of the nine frame stages (canvas.py, depth.py, deint.py, adeint.py, lut3d.py, interlace.py, signal.py, pal.py, probe.py), six
 entry points and a create of its own each (`_lib.frame_symbols`).  A family module declares short classes on `SourcePlan` / `EgressPlan` /
 `ResizePlan` / `FramePlan` — family name, C layout numbers or dtype, table function, frame size, its own arguments — and keeps what is truly
 its own; everything else is here."""

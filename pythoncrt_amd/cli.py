@@ -123,6 +123,17 @@ per frame as well as per line (on, the default: dot crawl).  NTSC-like only: no 
              --in-signal composite --signal-chroma soft --deinterlace edge --deinterlace-fields both [effect flags] |
       ffmpeg -f rawvideo -pix_fmt rgb24 -s 720x480 -r 60000/1001 -i - out.mp4
 
+`--signal-standard pal` makes that cable a PAL one (include/crtfx_pal.h) — PAL DVD, DVB, PAL-region consoles and home computers: the
+subcarrier turns 270 degrees per line and per frame, the V axis switches sign every line, and the decoder averages every line's chroma with
+the line above (`--pal-decoder delay`, the default) or does not (`simple`).  `--signal-phase DEGREES` (-180..180) is the decoder's phase
+error: under `delay` the picture loses saturation, under `simple` it shows Hanover bars.  `ntsc` (default) is the cable as it was; NTSC has
+no phase knob.  The rows of a woven frame are taken as consecutive lines; no 25 Hz offset, no RF noise.  A 576i DVD over composite:
+
+    ffmpeg -i dvd_576i.vob -f rawvideo -pix_fmt yuv420p - |
+      python -m pythoncrt_amd.cli --input - --width 720 --height 576 --fps 50 --output - --in-pix-fmt yuv420p --in-chroma-rows interlaced \
+             --in-signal composite --signal-standard pal --signal-phase 15 --deinterlace edge --deinterlace-fields both [effect flags] |
+      ffmpeg -f rawvideo -pix_fmt rgb24 -s 720x576 -r 50 -i - out.mp4
+
 `--in-lut FILE` / `--deliver-lut FILE` apply a 3D colour LUT (a `.cube` file, tetrahedral interpolation; include/crtfx_lut3d.h) on the
 GPU directly in front of the chain and directly behind it, at `--width x --height` and on the chain's pixels — the `lut3d=` of a second
 ffmpeg process and its round trip through host memory.  `--in-lut` brings a log-encoded or HDR source to display-referred video before
@@ -392,6 +403,14 @@ def add_input_flags(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--signal-crawl", type=str, default="on", choices=["on", "off"],
                    help="turn the subcarrier by 180 degrees per frame as well as per line (on, default: dot crawl) or per line only (off); needs "
                         "--in-signal")
+    p.add_argument("--signal-standard", type=str, default="ntsc", choices=["ntsc", "pal"],
+                   help="the colour standard of --in-signal: ntsc (default: include/crtfx_signal.h, 180 degrees per line) or pal "
+                        "(include/crtfx_pal.h: 270 degrees per line, the V switch and a delay-line decoder — 576i sources); needs --in-signal")
+    p.add_argument("--pal-decoder", type=str, default="delay", choices=["delay", "simple"],
+                   help="the PAL decoder: delay (default) averages every line's chroma with the line above, simple does not (a phase error "
+                        "then shows as Hanover bars); needs --signal-standard pal")
+    p.add_argument("--signal-phase", type=int, default=0, metavar="DEGREES",
+                   help="the PAL decoder's phase error in whole degrees, -180..180 (default 0); needs --signal-standard pal")
     return p
 
 
@@ -603,7 +622,7 @@ def check_flags(a):
             dither=a.dither, out_pix_fmt=a.out_pix_fmt, out_matrix=a.out_matrix, out_range=a.out_range, out_chroma=a.out_chroma,
             deliver_size=deliver_size_from_args(a), deliver_filter=a.deliver_filter, deliver_fit=a.deliver_fit, deliver_pad_color=(0, 0, 0),
             deliver_lut=None, deliver_interlace=a.deliver_interlace, deliver_lowpass=a.deliver_lowpass, in_chroma_rows=a.in_chroma_rows,
-            out_chroma_rows=a.out_chroma_rows)
+            out_chroma_rows=a.out_chroma_rows, signal_standard=a.signal_standard, pal_decoder=a.pal_decoder, signal_phase=a.signal_phase)
     try:
         refuse(v, "flags", early=True)
         if int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("CRTFX_FORCE_DIST") == "1":

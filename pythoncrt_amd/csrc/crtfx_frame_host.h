@@ -1,5 +1,5 @@
 // crtfx_frame_host.h — the host skeleton of the frame stages (crtfx_canvas.hip, crtfx_depth.hip, crtfx_deint.hip, crtfx_adeint.hip,
-// crtfx_lut3d.hip, crtfx_interlace.hip, crtfx_signal.hip): RGB frames in HBM to RGB frames in HBM, and what surrounds their kernels and does not depend on what the kernels do.
+// crtfx_lut3d.hip, crtfx_interlace.hip, crtfx_signal.hip, crtfx_pal.hip): RGB frames in HBM to RGB frames in HBM, and what surrounds their kernels and does not depend on what the kernels do.
 // Host code only, and everything here is a template or sits in an unnamed namespace, so every translation unit that includes it gets a
 // copy of its own: the units still share no state.  The device guard and the error helpers are those of the format stages
 // (crtfx_stage_host.h).  Unlike the format and resize stages these answer n == 0 with CRTFX_OK and look at no pointer then.

@@ -8,6 +8,7 @@ from .deint import Deinterlace
 from .depth import Narrow, Widen
 from .interlace import Interlace
 from .lut3d import Lut3D
+from .pal import PalSignal
 from .signal import Signal
 
 
@@ -51,20 +52,24 @@ class SourceEnd(StagingSlots):
     source's own samples, one pixel being one sample at four times the colour subcarrier — for an rgb24 frame at render size the only
     stage.  Its frame index t is the source frame's index in the stream: the caller sets `index` to that of the batch's first frame
     before convert() (0 until it does); several ends of one stream (a mixed-size rgb24 source) are each told.
+    `pal` is None or (decoder, phase): with a `signal`, a PalSignal (include/crtfx_pal.h) of those two values then stands in the Signal's
+    place — same size, sample type and index; it is `signal` too.
     `chroma_rows` says which luma rows a chroma row of a 4:2:0 source belongs to: "progressive" — rows 2c and 2c + 1, one of each field: in
     front of a Deinterlace, a Signal or a probe the colour of the two fields is then already mixed — or "interlaced" — the rows of its own
     field, as an interlaced encoder sub-samples them: the source plan is then an UnpackField420 (include/crtfx_field420.h) at `in_chroma`,
     and the stages behind it read fields whose colour is their own."""
 
     def __init__(self, device, render_hw, in_pix_fmt, in_matrix, in_range, in_chroma, src_hw, in_filter, crop=None, dtype=None, widen=False,
-                 deinterlace=None, lut=None, signal=None, chroma_rows="progressive"):
+                 deinterlace=None, lut=None, signal=None, chroma_rows="progressive", pal=None):
         import torch
         self.device, self.src_hw = device, tuple(src_hw)
         self.dtype = torch.uint8 if dtype is None or widen else dtype      # widen: `dtype` is the chain's, the stages in front of it run on uint8
         self.plan = formats.source_plan(device, self.src_hw, in_pix_fmt, in_matrix, in_range, in_chroma,
                                         *(() if chroma_rows == "progressive" else (chroma_rows,)))
         self.signal, self.index = None, 0
-        if signal is not None:
+        if signal is not None and pal is not None:
+            self.signal = PalSignal(device, self.src_hw, signal=signal[0], chroma=signal[1], crawl=signal[2], decoder=pal[0], phase=pal[1], dtype=self.dtype)
+        elif signal is not None:
             self.signal = Signal(device, self.src_hw, signal=signal[0], chroma=signal[1], crawl=signal[2], dtype=self.dtype)
         self.deint, self.ratio, self.adaptive = None, 1, False
         if deinterlace is not None:

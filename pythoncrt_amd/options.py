@@ -15,6 +15,7 @@ from .cube import Cube, as_cube
 from .deint import FIELDS, METHODS as SPATIAL, ORDERS
 from .depth import DITHERS
 from .interlace import LOWPASS, ORDERS as WEAVE_ORDERS
+from .pal import DECODERS, PHASES
 from .signal import CHROMAS, SIGNALS
 
 
@@ -37,6 +38,9 @@ class Raw(SimpleNamespace):
     crawl = property(lambda v: "on" if v.signal_crawl else "off")
     in_chroma_rows = "progressive"      # unless the surface says otherwise
     out_chroma_rows = "progressive"     # likewise
+    signal_standard = "ntsc"            # likewise: the three values of PAL_RULES
+    pal_decoder = "delay"
+    signal_phase = 0
 
     @property
     def src_rows(v):
@@ -195,10 +199,32 @@ OUT_FIELD_RULES = (
 )
 
 
+STANDARDS = ("ntsc", "pal")
+
+# What signal_standard adds, walked behind OUT_FIELD_RULES: a table of its own once more, every entry in front of the sharded CLI's branch.
+# "ntsc" is the Signal of in_signal as it was; "pal" puts a PalSignal in its place, and only that one has a decoder and a phase knob.
+PAL_RULES = (
+    Rule("signal_standard", lambda v: not isinstance(v.signal_standard, str) or v.signal_standard not in STANDARDS,
+         "signal_standard must be 'ntsc' or 'pal', got {v.signal_standard!r}", early=True),
+    Rule("pal_decoder", lambda v: not isinstance(v.pal_decoder, str) or v.pal_decoder not in DECODERS,
+         "pal_decoder must be 'delay' or 'simple', got {v.pal_decoder!r}", early=True),
+    Rule("signal_phase", lambda v: isinstance(v.signal_phase, bool) or not isinstance(v.signal_phase, int) or not PHASES[0] <= v.signal_phase <= PHASES[1],
+         "signal_phase must be an integer number of degrees in -180..180, got {v.signal_phase!r}",
+         "--signal-phase {v.signal_phase}: the decoder's phase error is a number of degrees in -180..180", early=True),
+    Rule("pal_off", lambda v: v.signal_standard == "ntsc" and (v.pal_decoder != "delay" or v.signal_phase != 0),
+         "pal_decoder={v.pal_decoder!r} / signal_phase={v.signal_phase!r} with signal_standard='ntsc': only the PAL decoder has a delay line and a phase knob",
+         "--pal-decoder {v.pal_decoder} / --signal-phase {v.signal_phase} without --signal-standard pal: only the PAL decoder has a delay line and "
+         "a phase knob", early=True),
+    Rule("pal_signal", lambda v: v.signal_standard == "pal" and v.in_signal == "rgb",
+         "signal_standard='pal' with in_signal='rgb': there is no signal to decode",
+         "--signal-standard pal without --in-signal composite | svideo: there is no signal to decode", early=True),
+)
+
+
 def refuse(v: Raw, surface: str, early: Optional[bool] = None) -> None:
-    """Walk RULES, then FIELD_RULES, then OUT_FIELD_RULES, over `v` for `surface` ("keywords" or "flags") and raise OptionError with the first message that
+    """Walk RULES, then FIELD_RULES, then OUT_FIELD_RULES, then PAL_RULES, over `v` for `surface` ("keywords" or "flags") and raise OptionError with the first message that
     applies.  `early`: only the entries in front of (True) or behind (False) the CLI's sharded branch."""
-    for rule in RULES + FIELD_RULES + OUT_FIELD_RULES:
+    for rule in RULES + FIELD_RULES + OUT_FIELD_RULES + PAL_RULES:
         text = getattr(rule, surface)
         if text is None or early not in (None, rule.early):
             continue
@@ -239,15 +265,22 @@ class ChainOptions:
     resize_on: str = "device"
     in_chroma_rows = "progressive"      # a constant here and a field of FieldChainOptions: see there
     out_chroma_rows = "progressive"     # likewise
+    signal_standard = "ntsc"            # constants here and fields of PalChainOptions / PalFieldChainOptions
+    pal_decoder = "delay"
+    signal_phase = 0
 
     @classmethod
     def build(cls, v: Raw, surface: Optional[str] = None) -> "ChainOptions":
         """The spec of raw values; with a surface they go through `refuse` first (OptionError), without one the caller has done that."""
         if surface is not None:
             refuse(v, surface)
-        if cls is ChainOptions and (v.in_chroma_rows != "progressive" or v.out_chroma_rows != "progressive"):
-            return FieldChainOptions.build(v)
-        rows = {} if cls is ChainOptions else {"in_chroma_rows": v.in_chroma_rows, "out_chroma_rows": v.out_chroma_rows}
+        if cls is ChainOptions:
+            fields, pal = v.in_chroma_rows != "progressive" or v.out_chroma_rows != "progressive", v.signal_standard == "pal"
+            if fields or pal:
+                return {(True, False): FieldChainOptions, (False, True): PalChainOptions, (True, True): PalFieldChainOptions}[fields, pal].build(v)
+        rows = {"in_chroma_rows": v.in_chroma_rows, "out_chroma_rows": v.out_chroma_rows} if issubclass(cls, FieldChainOptions) else {}
+        if "signal_standard" in cls.__dataclass_fields__:
+            rows.update(signal_standard=v.signal_standard, pal_decoder=v.pal_decoder, signal_phase=v.signal_phase)
         return cls(**rows, render_hw=v.render_hw, in_pix_fmt=v.in_pix_fmt, in_matrix=v.in_matrix, in_range=v.in_range, in_chroma=v.in_chroma,
                    in_size=None if v.in_size is None else v.src_hw, in_filter=v.in_filter, crop=v.in_crop,
                    deinterlace=None if v.deinterlace == "off" else (v.deinterlace, v.field_order, v.deinterlace_fields),
@@ -264,6 +297,7 @@ class ChainOptions:
     half = property(lambda self: self._depth()[0])          # the chain runs on half pixels: 10-bit formats on both ends, or chain_pix="half"
     widen = property(lambda self: self._depth()[1])         # the source's uint8 stages in front of a half chain end in a Widen
     narrow = property(lambda self: self._depth()[2])        # the dither of the Narrow in front of an 8-bit delivery behind a half chain, or None
+    pal = property(lambda self: (self.pal_decoder, self.signal_phase) if self.signal_standard == "pal" else None)   # the PalSignal's own two values
     ratio = property(lambda self: 2 if self.deinterlace is not None and self.deinterlace[2] == "both" else 1)      # frames the chain runs per source frame
 
     def batch(self, B: int) -> Tuple[int, int]:
@@ -286,7 +320,7 @@ class ChainOptions:
         from .ends import SourceEnd
         return SourceEnd(device, self.render_hw, self.in_pix_fmt, self.in_matrix, self.in_range, self.in_chroma, src_hw, self.in_filter, self.crop, pix,
                          widen=self.widen, deinterlace=self.deinterlace, **({} if self.in_cube is None else {"lut": self.in_cube}),
-                         **({} if self.signal is None else {"signal": self.signal}),
+                         **({} if self.signal is None else {"signal": self.signal}), **({} if self.pal is None else {"pal": self.pal}),
                          **({} if self.in_chroma_rows == "progressive" else {"chroma_rows": self.in_chroma_rows}))
 
     def delivery_end(self, device, pix):
@@ -305,3 +339,20 @@ class FieldChainOptions(ChainOptions):
     is one that the recorded cases of tests/test_chain_options.py move; "progressive" stays the base class's constant for both."""
     in_chroma_rows: str = "interlaced"
     out_chroma_rows: str = "progressive"
+
+
+@dataclass(frozen=True)
+class PalChainOptions(ChainOptions):
+    """The spec of a source that comes through the PAL cable: what `ChainOptions.build` returns for signal_standard="pal".  It carries the
+    three values of PAL_RULES; "ntsc" stays the base class's constant, for the reason FieldChainOptions gives."""
+    signal_standard: str = "pal"
+    pal_decoder: str = "delay"
+    signal_phase: int = 0
+
+
+@dataclass(frozen=True)
+class PalFieldChainOptions(FieldChainOptions):
+    """Both at once — 576i 4:2:0 through the PAL cable: the fields of FieldChainOptions and those of PalChainOptions."""
+    signal_standard: str = "pal"
+    pal_decoder: str = "delay"
+    signal_phase: int = 0

@@ -152,7 +152,8 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
                    dither: str = "none", deinterlace: str = "off", field_order: str = "tff", deinterlace_fields: str = "first",
                    in_lut=None, deliver_lut=None, deliver_interlace: str = "off", deliver_lowpass: str = "none",
                    in_signal: str = "rgb", signal_chroma: str = "sharp", signal_crawl: bool = True, in_chroma_rows: str = "progressive",
-                   out_chroma_rows: str = "progressive", **io_keywords) -> int:
+                   out_chroma_rows: str = "progressive", signal_standard: str = "ntsc", pal_decoder: str = "delay", signal_phase: int = 0,
+                   **io_keywords) -> int:
     """Render every frame of `frame_iter` (H x W x 3 uint8 RGB arrays) and hand the finished uint8 frames to `write_frame` in order.
     Effect keywords: the names, meaning and defaults of process_video / the CLI (ref:864-911, :1155-1206); the caller applies the clamps of
     ref:1225-1266 as the reference's `main` does (`pythoncrt_amd.cli.settings_from_args` restates them).  Returns the number of frames written.
@@ -325,6 +326,17 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
     `in_chroma_rows="interlaced"`, `deinterlace_fields="both"` and `deliver_interlace` an interlaced 4:2:0 round trip stays on the device.
     Refused with ValueError before a device is touched: an unknown value; "interlaced" with any other `out_pix_fmt`; a delivered height
     (`deliver_size`, or the render size) that is no multiple of 4.
+    `signal_standard="pal"` makes the cable of `in_signal` a PAL one — PAL DVD, DVB, PAL-region consoles and home computers, every 576i
+    source: a PalSignal (include/crtfx_pal.h) stands in the Signal's place, with the same `signal_chroma` and `signal_crawl` and the same
+    count of SOURCE frames.  Its subcarrier turns 270 degrees per line and per frame (only the index mod 4 matters) and the V axis switches
+    sign every line.  `pal_decoder="delay"` (default) is the delay-line decoder: every line's chroma is averaged with the line above (row 0
+    with row 1), which halves vertical chroma detail and turns a phase error into a loss of saturation; "simple" has no delay line, and a
+    phase error then shows as Hanover bars — even and odd lines turn their hue opposite ways.  `signal_phase` is that error, the
+    decoder's, in whole degrees -180..180 (default 0).  Pass it with `in_chroma_rows="interlaced"` for 576i 4:2:0.  "ntsc" (default)
+    is the path as it was: the Signal with the keywords it had, and no PalSignal is created; NTSC has no phase knob.  Stated limits: the
+    rows of a woven interlaced frame are taken as consecutive lines; no 25 Hz offset; no RF noise.  Refused with ValueError before a device
+    is touched: an unknown value; a `signal_phase` that is a bool, no integer or outside -180..180; `pal_decoder` or `signal_phase` off
+    its default under "ntsc"; "pal" with `in_signal="rgb"`.
     If `frame_iter` or `write_frame` raises, the GPU work already queued is drained (device synchronize) before the exception leaves this
     function, so that the staging buffers are not freed under a running copy."""
     import os
@@ -342,7 +354,8 @@ def process_frames(frame_iter: Iterable[np.ndarray], write_frame: Callable[[np.n
         deliver_pad_color=deliver_pad_color, chain_pix=chain_pix, dither=dither, deinterlace=deinterlace, field_order=field_order,
         deinterlace_fields=deinterlace_fields, in_lut=in_lut, deliver_lut=deliver_lut, deliver_interlace=deliver_interlace,
         deliver_lowpass=deliver_lowpass, in_signal=in_signal, signal_chroma=signal_chroma, signal_crawl=signal_crawl,
-        in_chroma_rows=in_chroma_rows, out_chroma_rows=out_chroma_rows), "keywords")
+        in_chroma_rows=in_chroma_rows, out_chroma_rows=out_chroma_rows, signal_standard=signal_standard, pal_decoder=pal_decoder,
+        signal_phase=signal_phase), "keywords")
     crop, ratio, deep = spec.crop, spec.ratio, formats.bits(in_pix_fmt) == 10
     if not torch.cuda.is_available():
         raise RuntimeError("no ROCm device visible; pythoncrt_amd has no CPU fallback")
